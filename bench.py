@@ -2,6 +2,18 @@
 """Benchmark of the 4K-NeRF rendering hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                             (also every side measurement and check listed below)
+    python bench.py ... --dump-outputs DIR                 (the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line with the headline only: ``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the timed region's own statistics.  Everything else -- the
+isolated-call roofline and sample counters, the other sharding mode, the 4K pipeline in every decoder arithmetic, the
+training legs, the reference pipeline, other scenes and sizes, the CPU baselines and parity checks -- runs only with
+``--full``, where ``--no-extras`` / ``--no-cpu-baseline`` / ``--sr-frames`` trim it as before.
+
+``--dump-outputs DIR`` writes what the caller of the timed path receives from the LAST timed step, after the timed region:
+``rgb_marched.npy`` [rays, 3], ``depth.npy`` [rays] and ``alphainv_last.npy`` [rays] (float32, the whole frame: 15 MB).  The scene
+and the pose sequence are seeded, so the same arguments give the same inputs on every run.
 
 Metric (BASELINE.json): Mrays/s on LLFF-fern ``render_test``.  A *step* is one full 1008x756 frame
 (762,048 rays x 256 samples) of BASELINE configs[1] -- "LLFF fern_lg_pretrain render_test at 1008x756,
@@ -20,7 +32,7 @@ asynchronous ``all_gather_into_tensor`` (RCCL) per frame moves the final 5 float
 form: rank r renders frames r, r+N, ... (weak).  The 4K pipeline (``four_k``, BASELINE configs[2]/[3]) shards the SR tiles of
 ONE frame over the ranks with one all-gather of the final HR pixels (strong).
 
-Objects on the JSON line (rank 0):
+Objects on the JSON line (rank 0; all but ``value`` and the other headline fields come with ``--full`` only):
   roofline         -- dominant kernels (fused marcher call), HBM bound: algorithmic bytes per launch (device counters,
                       SURVEY.md 8d formula) / mean ISOLATED launch time; ``traffic`` = fabric bytes per launch from the committed
                       rocprofv3 PMC passes of this command (profiles/*_marcher_traffic.json, the newest).  It also carries the scalars of
@@ -75,7 +87,14 @@ def parse():
     ap.add_argument('--same-device', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--sr-frames', type=int, default=12, help='4K frames (march + SFTNet x4, test_tile=510) timed for the '
                     'secondary frames/s figure (0 disables)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also run the side measurements and checks (roofline of the isolated call, '
+                    'other sharding mode, 4K pipeline, training legs, CPU baselines, parity); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 class MarcherRun:
@@ -84,7 +103,8 @@ class MarcherRun:
     def __init__(self, model, poses, rk, H, W, K, dev, world, rank, by_rows, n_streams):
         from nerf4k_amd import tile_parallel as tp
         from nerf4k_amd.lib import dvgo
-        self.model, self.rk, self.W, self.dev, self.world, self.by_rows = model, rk, W, dev, world, by_rows
+        self.model, self.rk, self.H, self.W, self.dev, self.world, self.by_rows = model, rk, H, W, dev, world, by_rows
+        self.last = None                     # (step index, returned dict) of the last timed step
         r0, r1, rows_per = tp.shard_rows(H, world, rank) if by_rows else (0, H, H)
         if world > 1 and not by_rows:          # rank r renders frames r, r+N, r+2N, ... of the pose sequence
             poses = [poses[(rank + i * world) % len(poses)] for i in range(len(poses))]
@@ -143,7 +163,8 @@ class MarcherRun:
             torch.cuda.synchronize()
             t_start = time.perf_counter()
             for i in range(steps):
-                self.step(i, timed=ev[i])
+                out = self.step(i, timed=ev[i])
+            self.last = (steps - 1, out)
             self.host_issue_ms_per_step = (time.perf_counter() - t_start) / max(steps, 1) * 1e3      # the host's share: issue only
             self.sync()
             elapsed = time.perf_counter() - t_start
@@ -156,6 +177,25 @@ class MarcherRun:
         S = len(self.streams)
         self.frame_intervals_ms = [ev[i - S][1].elapsed_time(ev[i][1]) / S for i in range(S, steps)]
         return float(t.item()), float(np.mean([a.elapsed_time(b) for a, b in ev]))
+
+    def final_outputs(self):
+        """The arrays a caller of the timed path holds after the last timed step of run(): per-ray rgb, depth and alphainv_last of
+        the whole frame (row bands: the all-gathered frame, which every rank holds).  Valid until the next call on this object."""
+        i, out = self.last
+        names = ('rgb_marched', 'depth', 'alphainv_last')
+        if not (self.by_rows and self.world > 1):
+            return {k: out[k] for k in names}
+        from nerf4k_amd import tile_parallel as tp
+        recv = self.recv[i & 1]
+        slot = recv.numel() // (5 * self.world)
+        parts = {k: [] for k in names}
+        for q in range(self.world):
+            r0, r1, _ = tp.shard_rows(self.H, self.world, q)
+            n, blk = (r1 - r0) * self.W, recv[q * 5 * slot:(q + 1) * 5 * slot]
+            parts['rgb_marched'].append(blk[:3 * n].view(n, 3))
+            parts['depth'].append(blk[3 * slot:3 * slot + n])
+            parts['alphainv_last'].append(blk[4 * slot:4 * slot + n])
+        return {k: torch.cat(v) for k, v in parts.items()}
 
     def isolated(self, n):
         """ISOLATED launch duration (one stream, HIP events around each call on the launch stream) and the device sample
@@ -275,19 +315,9 @@ def main():
     by_rows = world > 1 and args.shard == 'rows'
     run = MarcherRun(model, poses, rk, H, W, K, dev, world, rank, by_rows, args.streams)
     elapsed, overlapped_ms = run.run(args.steps, args.warmup)
-    nf = min(args.steps, len(run.rays))
-    iso_ms, counts = run.isolated(nf)
-    n_inb, n_mask, n_alpha, n_shade, n_behind = counts[:5]
-    n_band = run.n_band
-    secondary = None
-    if world > 1 and not args.no_extras:       # the other sharding mode, as a secondary field
-        other = MarcherRun(model, poses, rk, H, W, K, dev, world, rank, not by_rows, args.streams)
-        e2, _ = other.run(args.steps, args.warmup)
-        rays2 = H * W * (1 if not by_rows else world)
-        secondary = {'mode': 'rows+all_gather (strong)' if not by_rows else 'frames of the pose sequence per rank, no collective (weak)',
-                     'value': round(rays2 * args.steps / e2 / 1e6, 3), 'unit': 'Mrays/s', 'ms_per_step': round(e2 / args.steps * 1e3, 4)}
-        del other
-
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.final_outputs())
+    res = None
     if rank == 0:
         rays_per_step = H * W * (1 if (world == 1 or by_rows) else world)     # frames mode: every rank renders a frame per step
         # value: whole-job throughput of the timed region = rays / ms_per_step, the figure the driver's own clock can check (round 4 led with
@@ -295,9 +325,6 @@ def main():
         med_ms = float(np.median(run.frame_intervals_ms)) if run.frame_intervals_ms else elapsed / args.steps * 1e3
         eff_ms = elapsed / args.steps * 1e3            # per-frame time of the timed region (frames overlap on the streams)
         value = rays_per_step / (eff_ms * 1e-3) / 1e6
-        b_alg = n_band * 56 + n_inb * 1 + n_mask * 32 + n_shade * 8 * model.k0_dim * 4
-        achieved = b_alg / (iso_ms * 1e-3) / 1e9
-        traffic, traffic_src, roof2 = (None, None, None) if args.small else newest_traffic_profile()
         res = {
             'metric': 'Mrays/s, LLFF-fern render_test (HIP ray-marcher, 1008x756 frames)',
             'value': round(value, 3), 'value_basis': 'rays per frame / ms_per_step (mean over the timed region; frames pipelined on 3 HIP streams)',
@@ -315,6 +342,44 @@ def main():
                        'parallelism': ('single GPU' if world == 1 else
                                        f'ONE frame split in {world} row bands + RCCL all_gather of the final pixels' if by_rows else
                                        f'frames of the pose sequence sharded over {world} GPUs (full model replica each, no collective)')},
+        }
+    if args.full:
+        side_measurements(args, res, run, overlapped_ms, model, ck, poses, rk, H, W, K, dev, world, rank, by_rows)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of ``arrays`` as float32 ``out_dir/<name>.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().to(torch.float32).cpu().numpy())
+
+
+def side_measurements(args, res, run, overlapped_ms, model, ck, poses, rk, H, W, K, dev, world, rank, by_rows):
+    """--full: everything the JSON line carries besides the headline, added to ``res`` in place on rank 0.  Every rank runs it (at
+    N > 1 the isolated calls, the other sharding mode and the 4K / training legs synchronise the ranks)."""
+    nf = min(args.steps, len(run.rays))
+    iso_ms, counts = run.isolated(nf)
+    n_inb, n_mask, n_alpha, n_shade, n_behind = counts[:5]
+    n_band = run.n_band
+    secondary = None
+    if world > 1 and not args.no_extras:       # the other sharding mode, as a secondary field
+        other = MarcherRun(model, poses, rk, H, W, K, dev, world, rank, not by_rows, args.streams)
+        e2, _ = other.run(args.steps, args.warmup)
+        rays2 = H * W * (1 if not by_rows else world)
+        secondary = {'mode': 'rows+all_gather (strong)' if not by_rows else 'frames of the pose sequence per rank, no collective (weak)',
+                     'value': round(rays2 * args.steps / e2 / 1e6, 3), 'unit': 'Mrays/s', 'ms_per_step': round(e2 / args.steps * 1e3, 4)}
+        del other
+
+    if rank == 0:
+        b_alg = n_band * 56 + n_inb * 1 + n_mask * 32 + n_shade * 8 * model.k0_dim * 4
+        achieved = b_alg / (iso_ms * 1e-3) / 1e9
+        traffic, traffic_src, roof2 = (None, None, None) if args.small else newest_traffic_profile()
+        res.update({
             'mrays_isolated': round(n_band / (iso_ms * 1e-3) / 1e6, 3),
             'roofline': {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
@@ -330,7 +395,7 @@ def main():
                                 'samples_per_launch': {'in_bbox': int(n_inb), 'mask': int(n_mask), 'alpha': int(n_alpha), 'shaded': int(n_shade),
                                                        'alpha_behind_stop': int(n_behind)},
                                 'behind_stop_fraction_of_alpha': round(n_behind / max(n_alpha, 1), 4)},
-        }
+        })
         if secondary is not None:
             res['frames_sharded' if by_rows else 'rows_sharded'] = secondary
     four_k = four_k_fp32 = four_k_fast = four_k_alt = four_k_b6 = None
@@ -411,10 +476,6 @@ def main():
                 res['parity_vs_oracle'] = parity
                 rl['parity_psnr_db'] = parity.get('psnr_rgb_db')
         assert len(rl) <= 20 and all(not isinstance(v, (dict, list)) for v in rl.values()), 'roofline: at most 20 scalar entries'
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def _side(fn, *a):

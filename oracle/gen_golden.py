@@ -10,6 +10,7 @@ Needs ``/root/reference`` (absent on the GPU box -- the fixtures travel instead)
   rays_*.npz  : reference ``get_rays_of_a_view`` (lib/dvgo.py:577-582).
   sr_*.npz    : UNMODIFIED reference ``SFTNet.forward`` / ``tile_process`` (lib/sr_esrnet.py);
                 weights from oracle.sr.make_state_dict(seed) (stored as the seed, not the tensors).
+  live_mpi_seed3.npz : reference ``DirectMPIGO`` on the small case of ``live_case()`` (``python -m oracle.gen_golden live``).
 """
 import io
 import contextlib
@@ -362,9 +363,27 @@ def gen_grad_joint(ref):
           f'{ng} marcher gradients, {len(names)} decoder gradients, samples {rr["weights"].numel()}')
 
 
+def live_case():
+    """The small seeded MPI case of tests/test_oracle_golden.py::test_reference_still_importable_and_live_equal -> (ck, rays)."""
+    ck = scene.make_llff_checkpoint(seed=3, num_voxels=16 * 16 * 14, mpi_depth=14)
+    ro, rd, vd = marcher.get_rays_of_a_view(18, 24, scene.LLFF_K * np.array([[24 / 1008], [24 / 1008], [1]], dtype=np.float32),
+                                            scene.llff_spiral_poses()[2], ndc=True)
+    return ck, [x.reshape(-1, 3) for x in (ro, rd, vd)]
+
+
+def gen_live(ref):
+    ck, rays = live_case()
+    with torch.no_grad():
+        want = _ref_model(ref, ck)(*rays, **ck['render_kwargs'])
+    _save_march('live_mpi_seed3', ck, rays, {k: want[k] for k in ('ray_id', 'rgb_marched')})
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     ref = ref_import.load_reference()
+    if len(sys.argv) > 1 and sys.argv[1] == 'live':
+        gen_live(ref)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == 'grad':
         gen_grad(ref)
         return
@@ -386,6 +405,7 @@ def main():
     gen_grad_sr(ref)
     gen_patch(ref)
     gen_grad_joint(ref)
+    gen_live(ref)
 
 
 if __name__ == '__main__':

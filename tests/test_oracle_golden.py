@@ -70,25 +70,29 @@ def test_tile_geometry_llff_510():
     assert sum(w * h for w, h in wh) == 797728
 
 
-@pytest.mark.skipif(not ref_import.available(), reason='reference tree only exists on the build container')
 def test_reference_still_importable_and_live_equal():
-    """Live re-check (build container only): reference classes vs oracle on a fresh random case."""
+    """Reference classes vs oracle on a fresh seeded case (oracle/gen_golden.py::live_case): against the reference's output stored in
+    tests/golden/live_mpi_seed3.npz, and -- where the reference tree exists (build container) -- against the live reference module too."""
     import contextlib, io
-    import nerf4k_amd  # noqa: F401
-    from nerf4k_amd import scene
-    ref = ref_import.load_reference()
-    ck = scene.make_llff_checkpoint(seed=3, num_voxels=16 * 16 * 14, mpi_depth=14)
-    ro, rd, vd = marcher.get_rays_of_a_view(18, 24, scene.LLFF_K * np.array([[24 / 1008], [24 / 1008], [1]], dtype=np.float32),
-                                            scene.llff_spiral_poses()[2], ndc=True)
-    rays = [x.reshape(-1, 3) for x in (ro, rd, vd)]
-    with contextlib.redirect_stdout(io.StringIO()):
-        m = ref.dmpigo.DirectMPIGO(**ck['model_kwargs'])
-    m.load_state_dict(ck['model_state_dict'])
-    with torch.no_grad():
-        want = m(*rays, **ck['render_kwargs'])
+    from oracle import gen_golden
+    ck, rays = gen_golden.live_case()
+    z = np.load(os.path.join(GOLDEN, 'live_mpi_seed3.npz'))
+    for k, v in zip(('rays_o', 'rays_d', 'viewdirs'), rays):            # the case is the one the vectors were made for
+        assert np.array_equal(v.numpy(), z['in/' + k]), k
+    for k, v in ck['model_state_dict'].items():
+        assert np.array_equal(v.numpy(), z['sd/' + k]), k
+    wants = [{k: torch.from_numpy(z['out/' + k]) for k in ('ray_id', 'rgb_marched')}]
+    if ref_import.available():
+        ref = ref_import.load_reference()
+        with contextlib.redirect_stdout(io.StringIO()):
+            m = ref.dmpigo.DirectMPIGO(**ck['model_kwargs'])
+        m.load_state_dict(ck['model_state_dict'])
+        with torch.no_grad():
+            wants.append(m(*rays, **ck['render_kwargs']))
     got = marcher.mpi_forward(ck['model_kwargs'], ck['model_state_dict'], *rays, **ck['render_kwargs'])
-    assert torch.equal(got['ray_id'], want['ray_id'])
-    assert torch.allclose(got['rgb_marched'], want['rgb_marched'], atol=1e-6)
+    for want in wants:
+        assert torch.equal(got['ray_id'], want['ray_id'])
+        assert torch.allclose(got['rgb_marched'], want['rgb_marched'], atol=1e-6)
 
 
 @pytest.mark.parametrize('name', ['grad_mpi', 'grad_dvgo'])

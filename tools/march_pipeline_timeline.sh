@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_mp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_mp -o run -- python $R/bench.py --streams ${STREAMS:-3} --steps 60 --warmup 12 --no-cpu-baseline --no-extras --sr-frames 0 > /tmp/mp.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_mp -o run -- python $R/bench.py --streams ${STREAMS:-3} --steps 60 --warmup 12 --no-cpu-baseline --full --no-extras --sr-frames 0 > /tmp/mp.log 2>&1
 f=$(find /tmp/prof_mp -name '*kernel_trace.csv' | head -1)
 python - <<PY
 import csv, json

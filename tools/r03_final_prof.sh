@@ -7,13 +7,13 @@ mkdir -p $O
 cd $R
 COMMIT=${1:-unknown}
 if [ "$SKIP_TESTS" != "1" ]; then timeout 1500 python -m pytest tests -m gpu -q -x > $O/tests_gpu.log 2>&1; echo "gpu_tests_rc=$?"; tail -3 $O/tests_gpu.log; fi
-timeout 900 python bench.py > $O/bench_default.log 2>&1; echo "bench_rc=$?"; grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default_line.json
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench_rc=$?"; grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default_line.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_m $R/gpurun_out/prof_s
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_m -o run -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --sr-frames 0 --streams 1 > $O/prof_m.log 2>&1
-f=$(find $R/gpurun_out/prof_m -name "*kernel_stats.csv" | head -1); head -14 "$f" > $O/marcher_kernel_stats.csv
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_m -o run -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --full --no-extras --sr-frames 0 --streams 1 > $O/prof_m.log 2>&1
+f=$(find $O/prof_m -name "*kernel_stats.csv" | head -1); head -14 "$f" > $O/marcher_kernel_stats.csv
 grep '"metric"' $O/prof_m.log | tail -1 > $O/marcher_bench_line_under_rocprof.json
-rm -rf $R/gpurun_out/prof_m
+rm -rf $O/prof_m
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_s -o run -- python $R/tools/sr_frame_time.py f16x3 > $O/prof_s.log 2>&1
 f=$(find $R/gpurun_out/prof_s -name "*kernel_stats.csv" | head -1); head -14 "$f" > $O/sr_kernel_stats.csv
 grep "ms/frame" $O/prof_s.log > $O/sr_line.txt

@@ -7,13 +7,13 @@ O=$R/gpurun_out/r4final
 mkdir -p $O
 cd $R
 COMMIT=${1:-unknown}
-if [ "$SKIP_BENCH" != "1" ]; then timeout 900 python bench.py > $O/bench_default.log 2>&1; echo "bench_rc=$?"; grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default_line.json; python tools/bench_summary.py $O/bench_default_line.json; fi
+if [ "$SKIP_BENCH" != "1" ]; then timeout 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench_rc=$?"; grep '"metric"' $O/bench_default.log | tail -1 > $O/bench_default_line.json; python tools/bench_summary.py $O/bench_default_line.json; fi
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/prof_m $R/gpurun_out/prof_s
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_m -o run -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras --sr-frames 0 --streams 1 > $O/prof_m.log 2>&1
-f=$(find $R/gpurun_out/prof_m -name "*kernel_stats.csv" | head -1); head -14 "$f" > $O/marcher_kernel_stats.csv
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_m -o run -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --full --no-extras --sr-frames 0 --streams 1 > $O/prof_m.log 2>&1
+f=$(find $O/prof_m -name "*kernel_stats.csv" | head -1); head -14 "$f" > $O/marcher_kernel_stats.csv
 grep '"metric"' $O/prof_m.log | tail -1 > $O/marcher_bench_line_under_rocprof.json
-rm -rf $R/gpurun_out/prof_m
+rm -rf $O/prof_m
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_s -o run -- python $R/tools/sr_frame_time.py f16x3p > $O/prof_s.log 2>&1
 f=$(find $R/gpurun_out/prof_s -name "*kernel_stats.csv" | head -1); head -16 "$f" > $O/sr_kernel_stats.csv
 grep "ms/frame" $O/prof_s.log > $O/sr_line.txt
@@ -22,7 +22,7 @@ i=0
 for g in "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" \
          "TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do
   out=$R/gpurun_out/pmc_r4m_$i; rm -rf $out
-  timeout 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d $out -o run -- python $R/bench.py --steps 3 --warmup 1 --sr-frames 0 --no-cpu-baseline --no-extras --streams 1 > $out.log 2>&1 || echo "marcher pmc group $i failed"
+  timeout 300 rocprofv3 --pmc $g --kernel-trace --output-format csv -d $out -o run -- python $R/bench.py --steps 3 --warmup 1 --sr-frames 0 --no-cpu-baseline --full --no-extras --streams 1 > $out.log 2>&1 || echo "marcher pmc group $i failed"
   i=$((i+1))
 done
 python $R/tools/pmc_summary.py $R/gpurun_out/pmc_r4m_* > $O/marcher_pmc.md 2>&1

@@ -27,7 +27,7 @@ timeout 600 python -m pytest tests/test_sr_train_gpu.py tests/test_optim_gpu.py 
 for v in "PRE_STREAMS=0" "PRE_STREAMS=6" "PRE_STREAMS=12" "PRE_STREAMS=3" "PRE_STREAMS=9"; do
   env $v python /tmp/dbg2.py 2>/dev/null | tail -1
 done
-timeout 1500 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err; echo bench_rc=$?
+timeout 1500 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err; echo bench_rc=$?
 python tools/bench_summary.py $O/bench_default_line.json 2>/dev/null | tail -3
 python -c "
 import json; d=json.load(open('$O/bench_default_line.json'))['joint_train_step']; print({k: d[k] for k in ('ms_per_iteration','ms_per_iteration_blocks','ms_per_iteration_per_block_graph','breakdown_ms')})"
