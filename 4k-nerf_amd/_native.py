@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 14
+K4_ABI_VERSION = 15
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -27,6 +27,18 @@ class GridDesc(C.Structure):
                 ('act_depth', C.c_int32), ('mask_dims', C.c_int32 * 3),
                 ('xyz_min', C.c_float * 3), ('xyz_max', C.c_float * 3),
                 ('xyz2ijk_scale', C.c_float * 3), ('xyz2ijk_shift', C.c_float * 3), ('occ_summary', C.c_void_p), ('depth_split', C.c_int32)]
+
+
+class ContractedDesc(C.Structure):     # k4_contracted_desc (ABI 15)
+    _fields_ = [('rays_o', C.c_void_p), ('rays_d', C.c_void_p), ('viewdirs', C.c_void_p), ('n_rays', C.c_int64),
+                ('t_tab', C.c_void_p), ('s_tab', C.c_void_p), ('n_max', C.c_int32),
+                ('scene_center', C.c_float * 3), ('scene_radius', C.c_float * 3), ('bg_len', C.c_float), ('dist_thres', C.c_float), ('norm_l2', C.c_int32),
+                ('density', C.c_void_p), ('k0', C.c_void_p), ('k0_ch', C.c_int32), ('dims', C.c_int32 * 3), ('xyz_min', C.c_void_p), ('xyz_max', C.c_void_p),
+                ('mask', C.c_void_p), ('mask_dims', C.c_int32 * 3), ('xyz2ijk_scale', C.c_void_p), ('xyz2ijk_shift', C.c_void_p),
+                ('act_shift', C.c_float), ('interval', C.c_float), ('fast_color_thres', C.c_float), ('bg', C.c_float),
+                ('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p), ('w3', C.c_void_p), ('b3', C.c_void_p),
+                ('dim0', C.c_int32), ('width', C.c_int32), ('n_hidden', C.c_int32), ('viewfreq', C.c_void_p), ('n_pe', C.c_int32),
+                ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_last', C.c_void_p), ('counters', C.c_void_p)]
 
 
 class MlpDesc(C.Structure):
@@ -106,6 +118,7 @@ _SIGS = {
     'k4_segment_sum_backward': [_P, _P, _I64, _I32, _P, _P],
     'k4_get_rays_of_a_view': [_I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P],
     'k4_to8b': [_P, _I64, _P, _P],
+    'k4_cumdist_thres': [_P, _I64, _I64, _F, _P, _P],
     'k4_repack_k0': [_P, _I32, _I32, _I64, _P, _P],
     'k4_train_select_mpi': [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _F, _F, _P, _P, _P, _P, _P],
     'k4_train_compact': [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P],
@@ -211,6 +224,7 @@ _EXTRA_SIGS = {
     'k4_joint_losses_fwd': ([_P, _P, _P, _P, _P], C.c_int),
     'k4_joint_losses_bwd': ([_P, _P, _P, _P, _P, _P, _P], C.c_int),
     'k4_distortion_loss': ([_P, _P, _P, _I64, _I64, _F, _P, _P, _P], C.c_int),
+    'k4_march_contracted_fwd': ([C.POINTER(ContractedDesc), _P], C.c_int),
     'k4_nhwc_window_to_planar': ([_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P], C.c_int),
     'k4_tape_begin': ([_P], C.c_void_p),
     'k4_tape_end': ([_P], C.c_int),

@@ -572,6 +572,24 @@ __global__ void k_rays_of_view(int H, int W, const float* __restrict__ Kd, const
     for (int a = 0; a < 3; ++a) { ro[p * 3 + a] = o[a]; rd[p * 3 + a] = v[a]; }
 }
 
+// ---------------------------------------------------------------- ub360_utils_cuda.cumdist_thres (lib/cuda/ub360_utils_kernel.cu:12-32)
+// DirectContractedVoxGO's "skip oversampled points": per ray, c += dist[i]; over = c > thres; c *= !over; mask[i] = over.  The decision
+// chain is sequential fp32 with reset, so one thread walks one ray in order with the reference's own adds (no prefix-sum rewrite: that
+// rounds differently and moves resets).  The staged path's op; the fused inference kernel below runs the same chain without the table.
+__global__ void k_cumdist_thres(const float* __restrict__ dist, float thres, int64_t n_rays, int64_t n_pts, uint8_t* __restrict__ mask) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rays) return;
+    const float* __restrict__ d = dist + r * n_pts;
+    uint8_t* __restrict__ m = mask + r * n_pts;
+    float c = 0.f;
+    for (int64_t i = 0; i < n_pts; ++i) {
+        c = __fadd_rn(c, d[i]);
+        const bool over = c > thres;
+        c = __fmul_rn(c, (float)(!over));
+        m[i] = over;
+    }
+}
+
 // ---------------------------------------------------------------- utils.to8b (lib/utils.py:19): (255*clip(x,0,1)).astype(uint8)
 __global__ void k_to8b(const float* __restrict__ x, int64_t n, uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1028,6 +1046,280 @@ extern "C" int k4_to8b(const float* x, int64_t n, uint8_t* out, void* stream) {
     if (n == 0) return K4_OK;
     REQ(x && out);
     hipLaunchKernelGGL(k_to8b, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, x, n, out);
+    return k4_check_launch();
+}
+// ---------------------------------------------------------------- DirectContractedVoxGO inference: ONE launch per call (k4_march_contracted_fwd)
+// The staged forward (lib/dcvgo.py) materialises an [N][n_max][3] point table (1,068 steps per ray at 320^3) and filters it three times with host
+// synchronisations.  Here one WAVE walks one ray, lanes = 64 consecutive steps, in depth order, and nothing per sample leaves the chip:
+//   point     p_k = o' + d' t_tab[k], o' = (o - c) / r, d' = d / |d|; norm (inf | l2); outside the unit ball p <- p / n ((1 + bg) - n^-1 bg)
+//             (torch's `bg_len / norm` is reciprocal * bg_len) -- every op rounded once, as the tensor expressions of sample_ray
+//   cumdist   dist_k = |p_k - p_(k-1)|; the sequential scan with reset of k4_cumdist_thres, run wave-uniformly over the 64 lanes in step
+//             order with the carry held across chunks: every decision is the sequential definition's (no prefix-sum rewrite)
+//   filters   keep = inner | cumdist; mask_cache (k4s_maskcache); density (k4s_grid_corners / blend) -> raw2alpha (k4s_raw2alpha) ->
+//             alpha > thres; the exact transmittance product of k_alpha2weight incl. the T < 1e-3 stop; w > thres
+//   shading   survivors are queued in LDS (step, w) and shaded 64 at a time, lane = survivor: k0 trilinear (channel-major grid),
+//             features [k0 | viewdirs | sin | cos] (lib/dcvgo.py:334-340), the Linear-ReLU rgbnet as fp32 FMA chains, sigmoid;
+//             sum w rgb, sum w s_tab[k] (depth), alphainv_last = T, rgb += T bg.
+// The arithmetic of every stage is the staged kernels' (shared k4s_* helpers), so fused and staged paths agree to the order of the final sums.
+struct K4ContractedArgs {
+    const float *ro, *rd, *vd; int64_t n_rays;
+    const float *t_tab, *s_tab; int n_max;
+    float cx, cy, cz, rx, ry, rz, bg_len, dist_thres; int norm_l2;
+    const float* density; const float* k0; int C, X, Y, Z; const float *mn, *mx;
+    const uint8_t* mask; int MX, MY, MZ; const float *sc, *sh;
+    float act_shift, interval, thres, bg;
+    const float *w1, *b1, *w2, *b2, *w3, *b3; int dim0, n_hidden; const float* viewfreq; int n_pe;
+    float *rgb, *depth, *ainv; unsigned long long* counters;
+};
+
+__device__ __forceinline__ void k4c_point(const K4ContractedArgs& A, const float (&o)[3], const float (&d)[3], int k, float (&p)[3], bool& inner) {
+    const float t = A.t_tab[k];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = __fadd_rn(o[a], __fmul_rn(d[a], t));
+    float n;
+    if (A.norm_l2) n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(p[0], p[0]), __fmul_rn(p[1], p[1])), __fmul_rn(p[2], p[2])));
+    else n = fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]));
+    inner = n <= 1.f;
+    if (!inner) {
+        const float f = __fsub_rn(__fadd_rn(1.f, A.bg_len), __fmul_rn(__frcp_rn(n), A.bg_len));
+#pragma unroll
+        for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fdiv_rn(p[a], n), f);
+    }
+}
+
+template <int WIDTH>
+__device__ __forceinline__ void k4c_shade(const K4ContractedArgs& A, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
+    size_t idx[8]; float w[8];
+    k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
+    const size_t plane = (size_t)A.X * A.Y * A.Z;
+    if (WIDTH == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-k4s_grid_blend(A.k0 + plane * c, idx, w)));
+        return;
+    }
+    float h[WIDTH > 0 ? WIDTH : 1];
+#pragma unroll
+    for (int j = 0; j < WIDTH; ++j) h[j] = A.b1[j];
+    const int P = A.n_pe;
+    const int nin = A.C + 3 + 6 * P;
+    for (int i = 0; i < nin; ++i) {
+        float x;
+        if (i < A.C) x = k4s_grid_blend(A.k0 + plane * i, idx, w);
+        else {
+            const int e = i - A.C;
+            if (e < 3) x = vd[e];
+            else {
+                const int q = e - 3, sc = q / (3 * P), r = q - sc * 3 * P, dd = r / P, f = r - dd * P;
+                const float v = __fmul_rn(vd[dd], A.viewfreq[f]);
+                x = sc == 0 ? sinf(v) : cosf(v);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < WIDTH; ++j) h[j] = fmaf(A.w1[(size_t)j * A.dim0 + i], x, h[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < WIDTH; ++j) h[j] = fmaxf(h[j], 0.f);
+    float out[3] = {A.b3[0], A.b3[1], A.b3[2]};
+    if (A.n_hidden == 0) {
+#pragma unroll
+        for (int j = 0; j < WIDTH; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = fmaf(A.w3[c * WIDTH + j], h[j], out[c]);
+    } else {
+        for (int j2 = 0; j2 < WIDTH; ++j2) {
+            float acc = A.b2[j2];
+#pragma unroll
+            for (int i = 0; i < WIDTH; ++i) acc = fmaf(A.w2[(size_t)j2 * WIDTH + i], h[i], acc);
+            acc = fmaxf(acc, 0.f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = fmaf(A.w3[c * WIDTH + j2], acc, out[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-out[c]));
+}
+
+template <int WIDTH>
+__global__ __launch_bounds__(64) void k_march_contracted(const K4ContractedArgs A) {
+    __shared__ int qk[128];
+    __shared__ float qw[128];
+    const int64_t ray = blockIdx.x;
+    if (ray >= A.n_rays) return;
+    const int lane = k4_lane();
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    float o[3], d[3], vd[3];
+    {
+        const float dx = A.rd[ray * 3 + 0], dy = A.rd[ray * 3 + 1], dz = A.rd[ray * 3 + 2];
+        const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        const float c[3] = {A.cx, A.cy, A.cz}, r[3] = {A.rx, A.ry, A.rz}, dv[3] = {dx, dy, dz};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            o[a] = __fdiv_rn(__fsub_rn(A.ro[ray * 3 + a], c[a]), r[a]);
+            d[a] = __fdiv_rn(dv[a], dn);
+            vd[a] = A.vd[ray * 3 + a];
+        }
+    }
+    const bool count = A.counters != nullptr;
+    float T = 1.f, cum = 0.f;
+    bool stopped = false;
+    int nq = 0;
+    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
+    unsigned long long c_pre = 0, c_mask = 0, c_alpha = 0, c_shade = 0;
+    auto shade_queue = [&](int n) {
+        if (lane < n) {
+            const int k = qk[lane];
+            const float wk = qw[lane];
+            float p[3]; bool in;
+            k4c_point(A, o, d, k, p, in);
+            float rgb[3];
+            k4c_shade<WIDTH>(A, p, vd, rgb);
+            acc_r = fmaf(wk, rgb[0], acc_r);
+            acc_g = fmaf(wk, rgb[1], acc_g);
+            acc_b = fmaf(wk, rgb[2], acc_b);
+            acc_d = fmaf(wk, A.s_tab[k], acc_d);
+        }
+    };
+    for (int base = 0; base < A.n_max; base += 64) {
+        if (stopped && !count) break;
+        const int k = base + lane;
+        const bool valid = k < A.n_max;
+        float p[3] = {0.f, 0.f, 0.f}, q[3] = {0.f, 0.f, 0.f};
+        bool inner = false, in_prev = false;
+        float dist = 0.f;
+        if (valid) {
+            k4c_point(A, o, d, k, p, inner);
+            if (k > 0) {
+                k4c_point(A, o, d, k - 1, q, in_prev);
+                const float ex = __fsub_rn(p[0], q[0]), ey = __fsub_rn(p[1], q[1]), ez = __fsub_rn(p[2], q[2]);
+                dist = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)));
+            }
+        }
+        // the cumdist scan: wave-uniform carry, steps in order (k4_cumdist_thres's chain on dist[k - 1] = |p_k - p_(k-1)|)
+        bool over_me = false;
+        const int lim = min(64, A.n_max - base);
+        for (int l = 0; l < lim; ++l) {
+            if (base + l == 0) continue;
+            cum = __fadd_rn(cum, k4_readlane(dist, l));
+            const bool over = cum > A.dist_thres;
+            cum = __fmul_rn(cum, (float)(!over));
+            if (lane == l) over_me = over;
+        }
+        bool keep = valid && (inner || over_me);
+        if (keep) keep = k4s_maskcache(A.mask, p[0], p[1], p[2], A.sc, A.sh, A.MX, A.MY, A.MZ) != 0;
+        const bool pre = valid && (inner || over_me);
+        float alpha = 0.f;
+        if (keep) {
+            size_t idx[8]; float w[8];
+            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
+            float e;
+            k4s_raw2alpha(k4s_grid_blend(A.density, idx, w), A.act_shift, A.interval, e, alpha);
+        }
+        const bool apass = keep && (A.thres > 0.f ? alpha > A.thres : true);
+        // transmittance: the exact sequential product of k_alpha2weight over the alpha-passing samples in step order
+        float myw = 0.f;
+        bool wpass = false;
+        uint64_t bm = __ballot(apass);
+        while (bm && !stopped) {
+            const int l = __builtin_ctzll(bm);
+            const float al = k4_readlane(alpha, l);
+            if (lane == l) myw = T * al;
+            T = fmaf(-T, al, T);
+            bm &= bm - 1;
+            if (T < 1e-3f) stopped = true;
+            if (lane == l) wpass = A.thres > 0.f ? myw > A.thres : true;
+        }
+        if (count) {
+            c_pre += __popcll(__ballot(pre));
+            c_mask += __popcll(__ballot(keep));
+            c_alpha += __popcll(__ballot(apass));
+        }
+        const uint64_t sm = __ballot(wpass);
+        const int ns = __popcll(sm);
+        c_shade += ns;
+        if (wpass) {
+            const int slot = nq + __popcll(sm & below);
+            qk[slot] = k;
+            qw[slot] = myw;
+        }
+        nq += ns;
+        __syncthreads();
+        if (nq >= 64) {
+            shade_queue(64);
+            __syncthreads();
+            int rest = nq - 64, mk = 0; float mw = 0.f;
+            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
+            __syncthreads();
+            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
+            __syncthreads();
+            nq = rest;
+        }
+    }
+    shade_queue(nq);
+    // per-ray sums: wave reduction in a fixed lane order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_r += __shfl_down(acc_r, off);
+        acc_g += __shfl_down(acc_g, off);
+        acc_b += __shfl_down(acc_b, off);
+        acc_d += __shfl_down(acc_d, off);
+    }
+    if (lane == 0) {
+        A.rgb[ray * 3 + 0] = fmaf(T, A.bg, acc_r);
+        A.rgb[ray * 3 + 1] = fmaf(T, A.bg, acc_g);
+        A.rgb[ray * 3 + 2] = fmaf(T, A.bg, acc_b);
+        A.depth[ray] = acc_d;
+        A.ainv[ray] = T;
+        if (count) {
+            if (!(A.thres > 0.f)) c_shade = c_alpha;          // no weight filter: every alpha sample is shaded (w = 0 behind the stop)
+            atomicAdd(&A.counters[0], c_pre);
+            atomicAdd(&A.counters[1], c_mask);
+            atomicAdd(&A.counters[2], c_alpha);
+            atomicAdd(&A.counters[3], c_shade);
+        }
+    }
+}
+
+extern "C" int k4_march_contracted_fwd(const k4_contracted_desc* g, void* stream) {
+    REQ(g && g->n_rays >= 0 && g->n_max > 0);
+    if (g->n_rays == 0) return K4_OK;
+    REQ(g->rays_o && g->rays_d && g->viewdirs && g->t_tab && g->s_tab && g->density && g->k0 && g->mask && g->xyz_min && g->xyz_max);
+    REQ(g->xyz2ijk_scale && g->xyz2ijk_shift && g->rgb && g->depth && g->alphainv_last);
+    REQ(g->dims[0] > 0 && g->dims[1] > 0 && g->dims[2] > 0 && g->mask_dims[0] > 0 && g->mask_dims[1] > 0 && g->mask_dims[2] > 0);
+    const int W = g->width;
+    if (W == 0) { REQ(g->k0_ch == 3); }
+    else {
+        if (W != 32 && W != 64 && W != 128) return K4_ERR_UNSUPPORTED;
+        REQ(g->n_hidden == 0 || g->n_hidden == 1);
+        REQ(g->n_pe >= 0 && g->dim0 == g->k0_ch + 3 + 6 * g->n_pe && (g->n_pe == 0 || g->viewfreq));
+        REQ(g->w1 && g->b1 && g->w3 && g->b3 && (g->n_hidden == 0 || (g->w2 && g->b2)));
+    }
+    K4ContractedArgs A;
+    A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays;
+    A.t_tab = g->t_tab; A.s_tab = g->s_tab; A.n_max = g->n_max;
+    A.cx = g->scene_center[0]; A.cy = g->scene_center[1]; A.cz = g->scene_center[2];
+    A.rx = g->scene_radius[0]; A.ry = g->scene_radius[1]; A.rz = g->scene_radius[2];
+    A.bg_len = g->bg_len; A.dist_thres = g->dist_thres; A.norm_l2 = g->norm_l2;
+    A.density = g->density; A.k0 = g->k0; A.C = g->k0_ch; A.X = g->dims[0]; A.Y = g->dims[1]; A.Z = g->dims[2];
+    A.mn = g->xyz_min; A.mx = g->xyz_max;
+    A.mask = g->mask; A.MX = g->mask_dims[0]; A.MY = g->mask_dims[1]; A.MZ = g->mask_dims[2]; A.sc = g->xyz2ijk_scale; A.sh = g->xyz2ijk_shift;
+    A.act_shift = g->act_shift; A.interval = g->interval; A.thres = g->fast_color_thres; A.bg = g->bg;
+    A.w1 = g->w1; A.b1 = g->b1; A.w2 = g->w2; A.b2 = g->b2; A.w3 = g->w3; A.b3 = g->b3; A.dim0 = g->dim0; A.n_hidden = g->n_hidden;
+    A.viewfreq = g->viewfreq; A.n_pe = g->n_pe;
+    A.rgb = g->rgb; A.depth = g->depth; A.ainv = g->alphainv_last; A.counters = (unsigned long long*)g->counters;
+    const dim3 grid((unsigned)g->n_rays), block(64);
+    switch (W) {
+        case 0:   hipLaunchKernelGGL(k_march_contracted<0>, grid, block, 0, ST, A); break;
+        case 32:  hipLaunchKernelGGL(k_march_contracted<32>, grid, block, 0, ST, A); break;
+        case 64:  hipLaunchKernelGGL(k_march_contracted<64>, grid, block, 0, ST, A); break;
+        default:  hipLaunchKernelGGL(k_march_contracted<128>, grid, block, 0, ST, A); break;
+    }
+    return k4_check_launch();
+}
+extern "C" int k4_cumdist_thres(const float* dist, int64_t n_rays, int64_t n_pts, float thres, uint8_t* mask, void* stream) {
+    REQ(n_rays >= 0 && n_pts >= 0);
+    if (n_rays == 0 || n_pts == 0) return K4_OK;
+    REQ(dist && mask);
+    hipLaunchKernelGGL(k_cumdist_thres, dim3(k4_blocks(n_rays)), dim3(K4_THREADS), 0, ST, dist, thres, n_rays, n_pts, mask);
     return k4_check_launch();
 }
 extern "C" int k4_resample_trilinear(const float* in, int32_t channels, int32_t x, int32_t y, int32_t z,

@@ -131,7 +131,8 @@ class JointTrainer:
     """Optimizers + one-iteration method of the joint loop.  ``render_kwargs`` as run_sr.py:690-702 builds them
     (``render_depth=True``; ``rand_bkgd`` for LLFF); ``n_train_images`` = len(rays_o_tr), the TV weights' divisor (:1008-1011)."""
 
-    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, use_graph=None):
+    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, use_graph=None,
+                 near_clip=None):
         if cfg_train.weight_pcp > 0 or cfg_train.weight_gan > 0:
             raise NotImplementedError('perceptual / GAN losses (run_sr.py:934-957) are outside the hot-path scope (SURVEY.md 8)')
         if num_cond != 1 or dim_rend != 3:
@@ -139,6 +140,7 @@ class JointTrainer:
         self.model, self.net_sr, self.cfg, self.group = model, net_sr, cfg_train, group
         self.render_kwargs = dict(render_kwargs)
         self.n_train_images, self.sr_ratio = n_train_images, sr_ratio
+        self.near_clip = near_clip                  # data_dict['near_clip'] (run_sr.py:971): the weight_nearclip term's distance, world units
         self.optimizer = utils.create_optimizer_or_freeze_model(model, cfg_train, global_step=0)                  # run_sr.py:640
         self._side_stream_updates()
         self.optimizer_sr = MaskedAdam([{'params': net_sr.parameters(), 'lr': cfg_train.lrate_srnet, 'kname': 'srnet',
@@ -211,7 +213,16 @@ class JointTrainer:
             p = rr['alphainv_last'].clamp(1e-6, 1 - 1e-6)
             out['entropy_last'] = -(p * torch.log(p) + (1 - p) * torch.log(1 - p)).mean() * cfg.weight_entropy_last
         if cfg.weight_nearclip > 0:
-            raise NotImplementedError("weight_nearclip needs the 't' / 'raw_density' keys no BASELINE configuration produces")
+            # run_sr.py:970-976: push down the density of the samples closer than near_clip (t in units of the scene radius)
+            if 't' not in rr or 'raw_density' not in rr:
+                raise ValueError(f"weight_nearclip > 0 needs the 't' / 'raw_density' keys of the forward dict, which {type(self.model).__name__} "
+                                 "does not return (DirectContractedVoxGO does)")
+            if self.near_clip is None:
+                raise ValueError("weight_nearclip > 0 needs JointTrainer(near_clip=data_dict['near_clip'])")
+            near_thres = self.near_clip / self.model.scene_radius[0].item()
+            density = rr['raw_density'][rr['t'] < near_thres]
+            if len(density):
+                out['nearclip'] = cfg.weight_nearclip * (density - density.detach()).sum()
         if cfg.weight_distortion > 0:
             out['distortion'] = cfg.weight_distortion * train_ops.flatten_eff_distloss(rr['weights'], rr['s'], 1 / rr['n_max'], rr['ray_id'],
                                                                                         n_rays=rr['alphainv_last'].shape[0])

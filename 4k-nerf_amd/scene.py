@@ -8,6 +8,7 @@ exercised by both the product modules and the oracle.
 
   * ``make_llff_checkpoint``  -- DirectMPIGO (NDC) scene, BASELINE configs 2-4
   * ``make_lego_checkpoint``  -- DirectVoxGO bounded scene, BASELINE config 1
+  * ``make_unbounded_checkpoint`` / ``unbounded_poses`` -- DirectContractedVoxGO (unbounded_inward) scene and its cameras
   * ``llff_spiral_poses`` / ``lego_pose`` / ``LLFF_K`` -- synthetic cameras
 """
 import math
@@ -223,6 +224,92 @@ def make_lego_checkpoint(seed=777, num_voxels=160 ** 3, rgbnet_dim=12, rgbnet_wi
                      'flip_x': False, 'flip_y': False, 'render_depth': True}
     return {'global_step': 0, 'model_kwargs': kwargs, 'model_state_dict': sd,
             'model_class': 'DirectVoxGO', 'render_kwargs': render_kwargs}
+
+
+UNBOUNDED_CENTER = (0.1, -0.05, 0.2)
+UNBOUNDED_RADIUS = 1.5
+
+
+def make_unbounded_checkpoint(seed=777, num_voxels=320 ** 3, contracted_norm='inf', rgbnet_dim=12, rgbnet_width=128, rgbnet_depth=3,
+                              viewbase_pe=4, alpha_init=1e-2, fast_color_thres=1e-4, stepsize=0.5, n_blobs=10, bg_len=0.2):
+    """DirectContractedVoxGO checkpoint (lib/dcvgo.py) of an unbounded, inward-facing scene: density blobs inside the inner cube plus
+    structure in the contracted shell (1 < norm < 1 + bg_len: the background), a ``mask_cache`` from the 3x3x3 max-pooled alpha.
+    ``model_kwargs`` are what the reference's get_kwargs() stores (xyz_min / xyz_max are the CONTRACTED box, bg_len is not stored);
+    the scene bbox lives in the ``scene_center`` / ``scene_radius`` buffers."""
+    g = _gen(seed)
+    center = torch.tensor(UNBOUNDED_CENTER, dtype=torch.float32)
+    radius = torch.full([3], UNBOUNDED_RADIUS, dtype=torch.float32)
+    xyz_min = torch.Tensor([-1, -1, -1]) - bg_len                       # lib/dcvgo.py:48-49
+    xyz_max = torch.Tensor([1, 1, 1]) + bg_len
+    # DirectContractedVoxGO._set_grid_resolution (lib/dcvgo.py:125-131), num_voxels_base = num_voxels
+    voxel_size = ((xyz_max - xyz_min).prod() / num_voxels).pow(1 / 3)
+    world_size = ((xyz_max - xyz_min) / voxel_size).long()
+    ws = world_size.tolist()
+    act_shift = torch.FloatTensor([np.log(1 / (1 - alpha_init) - 1)])
+    # Gaussian blobs with centres in the inner cube (|x| <= 0.7 of the unit cube) ...
+    ax = [_axis(xyz_min[i], xyz_max[i], ws[i]) for i in range(3)]
+    field = torch.zeros(ws)
+    X, Y, Z = torch.meshgrid(*ax, indexing='ij')
+    gb = g
+    for _ in range(n_blobs):
+        c = [float((torch.rand([], generator=gb) * 2 - 1) * 0.7) for _ in range(3)]
+        sg = [float(0.08 + 0.12 * torch.rand([], generator=gb)) for _ in range(3)]
+        a = float(22.0 * (0.75 + 0.5 * torch.rand([], generator=gb)))
+        field += a * torch.exp(-0.5 * (((X - c[0]) / sg[0]) ** 2 + ((Y - c[1]) / sg[1]) ** 2 + ((Z - c[2]) / sg[2]) ** 2))
+    # the background: a wall in the contracted shell, modulated around the sphere (a few opaque patches and gaps)
+    nrm = torch.maximum(torch.maximum(X.abs(), Y.abs()), Z.abs()) if contracted_norm == 'inf' else (X * X + Y * Y + Z * Z).sqrt()
+    mid = 1 + 0.5 * bg_len
+    shell = torch.exp(-0.5 * ((nrm - mid) / (0.12 * bg_len)) ** 2)
+    ph = [float(torch.rand([], generator=gb) * 6.28) for _ in range(3)]
+    mod = 0.5 + 0.5 * torch.sin(3.0 * X + ph[0]) * torch.sin(2.0 * Y + ph[1]) * torch.cos(2.5 * Z + ph[2])
+    field += 24.0 * shell * mod
+    density = (field - 8.0)[None, None].contiguous()
+    alpha = _raw2alpha(density, act_shift, 1.0)
+    mask = F.max_pool3d(alpha, kernel_size=3, padding=1, stride=1)[0, 0] > fast_color_thres
+    k0_dim = rgbnet_dim if rgbnet_dim > 0 else 3
+    k0 = _smooth3(torch.randn([1, k0_dim] + ws, generator=g) * 0.5).contiguous()
+    sd = {
+        'scene_center': center.clone(), 'scene_radius': radius.clone(),
+        'xyz_min': xyz_min.clone(), 'xyz_max': xyz_max.clone(), 'act_shift': act_shift,
+        'density.grid': density, 'density.xyz_min': xyz_min.clone(), 'density.xyz_max': xyz_max.clone(),
+        'k0.grid': k0, 'k0.xyz_min': xyz_min.clone(), 'k0.xyz_max': xyz_max.clone(),
+    }
+    if rgbnet_dim > 0:
+        sd['viewfreq'] = torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)])
+        sd.update(_rgbnet_state(g, 3 + 3 * viewbase_pe * 2 + k0_dim, rgbnet_width, rgbnet_depth, gain=1.5))   # lib/dcvgo.py:101-103
+    scale = (torch.tensor(list(mask.shape), dtype=torch.float32) - 1) / (xyz_max - xyz_min)
+    sd['mask_cache.mask'] = mask
+    sd['mask_cache.xyz2ijk_scale'] = scale
+    sd['mask_cache.xyz2ijk_shift'] = -xyz_min * scale
+    kwargs = {
+        'xyz_min': xyz_min.numpy().copy(), 'xyz_max': xyz_max.numpy().copy(),
+        'num_voxels': num_voxels, 'num_voxels_base': num_voxels, 'alpha_init': alpha_init,
+        'voxel_size_ratio': 1.0, 'mask_cache_world_size': list(mask.shape), 'fast_color_thres': fast_color_thres,
+        'contracted_norm': contracted_norm, 'density_type': 'DenseGrid', 'k0_type': 'DenseGrid', 'density_config': {}, 'k0_config': {},
+        'rgbnet_dim': rgbnet_dim, 'rgbnet_depth': rgbnet_depth, 'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe,
+    }
+    render_kwargs = {'near': 0., 'far': 1e9, 'bg': 1, 'stepsize': stepsize, 'inverse_y': False,
+                     'flip_x': False, 'flip_y': False, 'render_depth': True}
+    return {'global_step': 0, 'model_kwargs': kwargs, 'model_state_dict': sd,
+            'model_class': 'DirectContractedVoxGO', 'render_kwargs': render_kwargs}
+
+
+def unbounded_poses(n_frames=8, dist=0.8, height=0.15):
+    """Inward-facing 360-degree cameras: a circle of radius ``dist * UNBOUNDED_RADIUS`` around the scene centre (inside the inner cube
+    of the contracted domain), each looking at the centre.  -> [n,3,4] float32 c2w (OpenGL axes, as get_rays with inverse_y=False)."""
+    c = np.asarray(UNBOUNDED_CENTER, dtype=np.float64)
+    r = dist * UNBOUNDED_RADIUS
+    up = np.array([0., 0., 1.])
+    poses = []
+    for th in np.linspace(0., 2 * np.pi, n_frames + 1)[:-1]:
+        pos = c + np.array([r * np.cos(th), r * np.sin(th), height * UNBOUNDED_RADIUS])
+        poses.append(_viewmatrix(pos - c, up, pos))
+    return np.stack(poses, 0).astype(np.float32)
+
+
+def unbounded_K(H, W, fov_x=1.2):
+    focal = .5 * W / np.tan(.5 * fov_x)
+    return np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]], dtype=np.float32)
 
 
 # ---------------------------------------------------------------------------

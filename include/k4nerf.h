@@ -36,7 +36,7 @@ extern "C" {
 #define K4_ERR_BAD_ARG      10001   /* null pointer / non-positive size / unsupported combination */
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
-#define K4_ABI_VERSION      14      /* 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      15      /* 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -287,6 +287,29 @@ int k4_get_rays_of_a_view(int32_t H, int32_t W, const float* K_dev, const float*
                           int32_t inverse_y, int32_t flip_x, int32_t flip_y, int32_t mode_center, float focal,
                           float* rays_o, float* rays_d, float* viewdirs, void* stream);
 int k4_to8b(const float* x, int64_t n, uint8_t* out, void* stream);
+/* ABI 15 -- ub360_utils_cuda.cumdist_thres of DirectContractedVoxGO (lib/dcvgo.py:301-303, lib/cuda/ub360_utils_kernel.cu:12-32): dist [n_rays][n_pts]
+ * fp32, mask [n_rays][n_pts] bytes (0 / 1).  Per ray, in step order: c += dist[i]; mask[i] = c > thres; c *= !mask[i] (c starts at 0) -- the
+ * sequential fp32 chain with reset, evaluated as written (every decision equals the sequential definition's). */
+int k4_cumdist_thres(const float* dist, int64_t n_rays, int64_t n_pts, float thres, uint8_t* mask, void* stream);
+/* ABI 15 -- DirectContractedVoxGO inference in ONE launch (lib/dcvgo.py:255-383 under torch.no_grad): per ray the contracted samples of the step table
+ * t_tab[n_max] (host-built with the reference's linspace expressions), the cumdist_thres filter (sequential, exact), mask_cache, trilinear density,
+ * raw2alpha with the uniform interval, alpha > thres, the exact transmittance product (T < 1e-3 stop), w > thres, k0 + viewdir PE + rgbnet (width
+ * 32 | 64 | 128, n_hidden 0 | 1; width 0 = coarse: sigmoid(k0), k0_ch == 3), and rgb = sum w rgb + T bg, depth = sum w s_tab[step], alphainv_last = T.
+ * Grids channel-major as stored ([C][X][Y][Z]), mask bytes [MX][MY][MZ], rgbnet weights as the nn.Linear tensors (w1 [width][dim0], dim0 =
+ * k0_ch + 3 + 6 n_pe; w2 [width][width]; w3 [3][width]).  counters: NULL or uint64[4] (ADDED to) = {inner|cumdist samples, mask-pass, alpha-pass,
+ * shaded}.  No workspace. */
+typedef struct k4_contracted_desc {
+    const float* rays_o; const float* rays_d; const float* viewdirs; int64_t n_rays;
+    const float* t_tab; const float* s_tab; int32_t n_max;
+    float scene_center[3]; float scene_radius[3]; float bg_len; float dist_thres; int32_t norm_l2;
+    const float* density; const float* k0; int32_t k0_ch; int32_t dims[3]; const float* xyz_min; const float* xyz_max;
+    const uint8_t* mask; int32_t mask_dims[3]; const float* xyz2ijk_scale; const float* xyz2ijk_shift;
+    float act_shift; float interval; float fast_color_thres; float bg;
+    const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3;
+    int32_t dim0; int32_t width; int32_t n_hidden; const float* viewfreq; int32_t n_pe;
+    float* rgb; float* depth; float* alphainv_last; uint64_t* counters;
+} k4_contracted_desc;
+int k4_march_contracted_fwd(const k4_contracted_desc* desc, void* stream);
 /* The interior of a decoded window into the frame (SFTNet.tile_process, lib/sr_esrnet.py:508-524: output_tile[..., crop] -> output[..., tile]) in ONE pass:
  * dst[c * dst_plane_stride + y * dst_row_stride + x] = src[((oy + y) * src_w + ox + x) * channels + c], 0 <= y < th, 0 <= x < tw, c < channels (<= 4);
  * src: the window's NHWC result [*][src_w][channels], dst: planes of the [1, 3, 4H, 4W] frame (pre-offset to the tile) or of a gather buffer. */
