@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 15
+K4_ABI_VERSION = 16
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -71,9 +71,7 @@ class RdbTrain(C.Structure):         # k4_rdb_train
                 ('dwdb', C.c_void_p * 5), ('gsft0', C.c_void_p * 8), ('gsft1', C.c_void_p * 8),
                 ('ws0', C.c_void_p), ('ws0_bytes', C.c_int64), ('ws1', C.c_void_p), ('ws1_bytes', C.c_int64), ('side_stream', C.c_void_p),
                 ('gc_acc', C.c_void_p), ('gx0_add', C.c_void_p), ('dwdb_span', C.c_void_p), ('dwdb_span_floats', C.c_int64),
-                ('fused_lrelu', C.c_int32), ('g5_from_gx0_add', C.c_int32), ('no_join', C.c_int32), ('defer_side', C.c_int32),
-                ('aux_stream', C.c_void_p), ('g5_next', C.c_void_p), ('gx0_add2', C.c_void_p), ('gx0_sum2', C.c_void_p),
-                ('g5_given', C.c_int32), ('aux_wgrad', C.c_int32)]
+                ('aux_stream', C.c_void_p), ('g5_next', C.c_void_p), ('gx0_add2', C.c_void_p), ('gx0_sum2', C.c_void_p), ('aux_wgrad', C.c_int32)]
 
 
 class AdamJob(C.Structure):          # k4_adam_job
@@ -210,8 +208,6 @@ _EXTRA_SIGS = {
     'k4_sft_train_fwd': ([_P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I32, _P], C.c_int),
     'k4_sft_train_fwd_ex': ([_P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I32, _P, _I32, _F, _P], C.c_int),
     'k4_sft_train_bwd_workspace_bytes': ([_I64, _I32], C.c_int64),
-    'k4_sft_train_bwd': ([_P, _I32, _P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P,
-                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
     'k4_sft_train_bwd_ex': ([_P, _I32, _P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P,
                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _F, _P], C.c_int),
     'k4_sft_train_bwd_side': ([_P, _I32, _P, _I32, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P,
@@ -294,7 +290,7 @@ def vec3(t):
 _OVERLAP_STREAMS = {}           # (device index, main stream handle, group) -> {tag: torch.cuda.ExternalStream}
 
 
-def overlapping_stream(device, tag, low_priority=False, group='training step', beside_main=True):
+def overlapping_stream(device, tag, group='training step', beside_main=True):
     """The side stream `tag` of the CURRENT stream on `device`: a stream verified to run beside the current stream and beside the streams the other tags of
     the same group already hold (include/k4nerf.h k4_stream_create_overlapping: HIP streams share a few hardware queues, and a "second stream" that
     lands on the main stream's queue serialises with it -- the joint training iteration took 9 ms or 21 ms depending on how many streams the process had
@@ -316,7 +312,7 @@ def overlapping_stream(device, tag, low_priority=False, group='training step', b
             return st
         arr = (C.c_void_p * max(1, len(others)))(*others)
         with torch.cuda.device(idx):
-            raw = lib().k4_stream_create_overlapping(C.c_void_p(first), arr, len(others), int(bool(low_priority)))
+            raw = lib().k4_stream_create_overlapping(C.c_void_p(first), arr, len(others), 0)
         if not raw:
             raise K4Error('k4_stream_create_overlapping failed')
         st = mine[tag] = torch.cuda.ExternalStream(raw, device=idx)

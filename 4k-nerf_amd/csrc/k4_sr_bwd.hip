@@ -39,7 +39,7 @@ __device__ __forceinline__ void wg_split3(const float (&v)[8], uint4& t0, uint4&
     t0 = make_uint4(p0[0], p0[1], p0[2], p0[3]); t1 = make_uint4(p1[0], p1[1], p1[2], p1[3]); t2 = make_uint4(p2[0], p2[1], p2[2], p2[3]);
 }
 
-// zero-fill as a KERNEL (not hipMemsetAsync): inside a hipGraph capture (lib/sr_train.GraphedDecoder) the memset of this ROCm build ran
+// zero-fill as a KERNEL (not hipMemsetAsync): inside a hipGraph capture (of lib/sr_train.forward_train by a caller) the memset of this ROCm build ran
 // once at capture time instead of becoming a node -- replays then added their split-K partial sums to stale contents
 __global__ void wg_zero_kernel(float* __restrict__ p, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1252,15 +1252,6 @@ extern "C" int k4_sft_train_bwd_ex(const float* x, int32_t x_stride, const float
                                  gw0s, gb0s, gw1s, gb1s, gw0h, gb0h, gw1h, gb1h, workspace, workspace_bytes, grad_x_add, gxa_stride, accumulate_grad_cond, grad_x_lrelu,
                                  grad_y_scale, nullptr, stream);
 }
-extern "C" int k4_sft_train_bwd(const float* x, int32_t x_stride, const float* cond, int32_t cond_stride, const float* grad_y, int32_t gy_stride,
-                                int64_t n_pix, int32_t channels,
-                                const float* w0s, const float* b0s, const float* w1s, const float* b1s, const float* w0h, const float* b0h, const float* w1h,
-                                float slope, float* grad_x, float* grad_cond,
-                                float* gw0s, float* gb0s, float* gw1s, float* gb1s, float* gw0h, float* gb0h, float* gw1h, float* gb1h,
-                                float* workspace, int64_t workspace_bytes, void* stream) {
-    return k4_sft_train_bwd_ex(x, x_stride, cond, cond_stride, grad_y, gy_stride, n_pix, channels, w0s, b0s, w1s, b1s, w0h, b0h, w1h, slope, grad_x, grad_cond,
-                               gw0s, gb0s, gw1s, gb1s, gw0h, gb0h, gw1h, gb1h, workspace, workspace_bytes, nullptr, 0, 0, 0, 1.f, stream);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // LeakyReLU backward on a channel slice (dense-block gradient image of the decoder's training graph, lib/sr_train.py K4RDB)
@@ -1346,7 +1337,8 @@ static bool k4_rdb_ok(const k4_rdb_train* p, bool bwd) {
     for (int k = 0; k < 5; ++k) if (!p->w_fwd[k] && !bwd) return false;
     for (int k = 0; k < 8; ++k) if (!p->sft0[k] || !p->sft1[k]) return false;
     if (!bwd) return p->out != nullptr;
-    if (!p->g5 || !p->G || !p->gx4 || !p->gx0 || !p->ws0 || !p->ws1 || (!p->gc_acc && (!p->gc0 || !p->gc1)) || p->dwdb_span_floats < 0) return false;
+    if (!p->g5 || !p->G || !p->gx4 || !p->gx0 || !p->ws0 || !p->ws1 || (!p->gc_acc && (!p->gc0 || !p->gc1)) || !p->gx0_add) return false;
+    if (!p->dwdb_span || p->dwdb_span_floats <= 0) return false;
     for (int k = 0; k < 5; ++k) if (!p->w_bwd[k] || !p->b_bwd[k] || !p->dwdb[k]) return false;
     for (int k = 0; k < 8; ++k) if (!p->gsft0[k] || !p->gsft1[k]) return false;
     return true;
@@ -1380,47 +1372,38 @@ extern "C" int k4_rdb_train_bwd(const k4_rdb_train* p_in, void* stream) {
     const int H = p->H, W = p->W, nf = p->nf, g = p->g, bw = nf + 4 * g;
     const int64_t n = (int64_t)H * W;
     hipStream_t main_s = (hipStream_t)stream, side = p->side_stream ? (hipStream_t)p->side_stream : main_s;
-    // every exit joins the side stream back into `stream`: after a failed launch the caller frees the gradient buffers on `stream` while weight
-    // gradients already forked to the side stream may still be running on them
+    // aux_stream (the launch tapes' form): every side-stream launch of the block (zero-fill, five weight gradients, two SFT reductions) is issued at the END of the
+    // block behind ONE fork and not joined here.  Forking per weight gradient put a hipEventRecord on the chain's stream in front of every dgrad launch: ~7 us of the
+    // chain's time each, 1.0 ms of a 4.1 ms backward pass (profiles/r06_joint_phase_events.md, section 8); a join per block made the chain wait ~40 us at every block.
+    // The chain runs only the grad_x part of the two SFT layers' backward (k4_sft_train_bwd_gx); the rest of both layers goes to aux_stream behind the same fork.
+    // The caller joins both streams before gc_acc's first reader and before the optimizer.
+    hipStream_t aux = (hipStream_t)p->aux_stream;
+    const bool split = aux != nullptr;
+    if (split ? (side == main_s || aux == main_s || !p->gc_acc) : (p->g5_next || p->gx0_add2 || p->gx0_sum2 || p->aux_wgrad)) return K4_ERR_BAD_ARG;
+    // every exit of the per-block form joins the side stream back into `stream`: after a failed launch the caller frees the gradient buffers on `stream` while
+    // weight gradients already forked to the side stream may still be running on them
     int rc = 0;
-    const bool fl = p->fused_lrelu != 0;
-    if (p->g5_from_gx0_add && !p->gx0_add) return K4_ERR_BAD_ARG;
 #undef K4_RDB_TRY
 #define K4_RDB_TRY(CALL) do { rc = (CALL); if (rc != 0) goto join; } while (0)
-    // a weight gradient on the side stream: forked behind everything queued on the main stream so far (= the producer of the gradient slice it reads)
-    // defer_side: every side-stream launch of the block (zero-fill, five weight gradients, two SFT reductions) is issued at the END of the block behind ONE fork.
-    // Forking per weight gradient put a hipEventRecord on the chain's stream in front of every dgrad launch: ~7 us of the chain's time each, 1.0 ms of a 4.1 ms
-    // backward pass (profiles/r06_joint_phase_events.md, section 8).  Needs a caller that does not join per block (no_join): the weight gradients of block b then
-    // run beside the chain of block b - 1.
-    const bool defer = p->defer_side != 0 && side != main_s;
-    // aux_stream (ABI 14; with defer_side + no_join + gc_acc): the chain runs only the grad_x part of the two SFT layers' backward (k4_sft_train_bwd_gx); the rest of
-    // both layers goes to aux_stream at the end of the block.  The caller joins aux_stream before grad_cond's first reader and before the optimizer.
-    hipStream_t aux = (hipStream_t)p->aux_stream;
-    const bool split = defer && p->no_join != 0 && p->gc_acc != nullptr && aux != nullptr && aux != main_s;
     struct WgradQ { int cin; const float* gy; int cout; int gys; int k; } wq[5];
     int nwq = 0;
+    // a weight gradient on the side stream: per block, forked behind everything queued on the main stream so far (= the producer of the gradient slice it reads);
+    // split: queued for the block's closing fork
 #define K4_RDB_WGRAD(CIN, GY, COUT, GYS, K) do { \
-        if (defer) { wq[nwq].cin = (CIN); wq[nwq].gy = (GY); wq[nwq].cout = (COUT); wq[nwq].gys = (GYS); wq[nwq].k = (K); ++nwq; break; } \
+        if (split) { wq[nwq].cin = (CIN); wq[nwq].gy = (GY); wq[nwq].cout = (COUT); wq[nwq].gys = (GYS); wq[nwq].k = (K); ++nwq; break; } \
         K4_RDB_TRY(k4_wait_stream(side, main_s)); \
-        if (p->dwdb_span_floats > 0) K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6_acc(p->buf, (CIN), bw, (GY), (COUT), (GYS), 3, H, W, p->dwdb[K], (void*)side)); \
-        else K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6(p->buf, (CIN), bw, (GY), (COUT), (GYS), 3, H, W, p->dwdb[K], (void*)side)); } while (0)
+        K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6_acc(p->buf, (CIN), bw, (GY), (COUT), (GYS), 3, H, W, p->dwdb[K], (void*)side)); } while (0)
     // G[:, 0:COUT'] (+)= dgrad: the output is its own residual
-    // MASK (fused_lrelu): the last 32 channels this launch completes are x_k's gradient slice -- LeakyReLU backward from buf's slice in the epilogue
+    // MASK: the last 32 channels this launch completes are x_k's gradient slice -- LeakyReLU backward from buf's slice in the epilogue
 #define K4_RDB_DGRAD(K, SRC, SS, CIN_OF_LAYER, ACC, MASK) \
         K4_RDB_TRY(k4_conv2d_nhwc_bf16x6((SRC), (K) == 4 ? nf : g, (SS), p->w_bwd[K], p->b_bwd[K], 3, p->G, (CIN_OF_LAYER), bw, H, W, \
                                          ((ACC) ? K4_EPI_RES : 0u) | ((MASK) ? K4_EPI_LRELU_BWD : 0u) | K4_CONV_SMALL, 0.2f, \
                                          (ACC) ? p->G : nullptr, (ACC) ? bw : 0, 1.f, (MASK) ? p->buf : nullptr, (MASK) ? bw : 0, stream))
-    // dwdb_span_floats > 0: the five [dW | dbias] buffers are one span starting at dwdb_span: ONE zero-fill on the side stream (ordered before every
-    // weight gradient there) instead of one per layer
-    if (p->dwdb_span_floats > 0) {
-        if (!p->dwdb_span) return K4_ERR_BAD_ARG;
-        if (!defer) {
-            K4_RDB_TRY(k4_wait_stream(side, main_s));                              // (the span may be memory the main stream's earlier work still reads)
-            K4_RDB_TRY(k4_zero_f32(p->dwdb_span, p->dwdb_span_floats, (void*)side));
-        }
-    }
-    if (!split && (p->g5_next || p->gx0_add2 || p->gx0_sum2)) return K4_ERR_BAD_ARG;        // by-products of the chain's grad_x launch (aux_stream form only)
-    if (p->g5_from_gx0_add && !p->g5_given) {                                       // g5 = 0.2 grad_out (conv5's output is scaled by 0.2 in the forward pass)
+    // the five [dW | dbias] buffers are one span starting at dwdb_span: ONE zero-fill on the side stream (ordered before every weight gradient there)
+    if (!split) {
+        K4_RDB_TRY(k4_wait_stream(side, main_s));                                  // (the span may be memory the main stream's earlier work still reads)
+        K4_RDB_TRY(k4_zero_f32(p->dwdb_span, p->dwdb_span_floats, (void*)side));
+        // g5 = 0.2 grad_out (conv5's output is scaled by 0.2 in the forward pass); split: the producer of gx0_add wrote it (g5_next / grad_x_scaled)
         const bool vec = (((uintptr_t)p->gx0_add | (uintptr_t)p->g5) & 15u) == 0;
         const int64_t units = vec ? n * nf / 4 : n * nf;
         if (vec) hipLaunchKernelGGL(k_scale_f32<true>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, main_s, p->gx0_add, 0.2f, (float*)p->g5, units);
@@ -1430,53 +1413,44 @@ extern "C" int k4_rdb_train_bwd(const k4_rdb_train* p_in, void* stream) {
     // conv5: out = 0.2 conv5(buf) + t
     K4_RDB_WGRAD(bw, p->g5, nf, nf, 4);
     K4_RDB_DGRAD(4, p->g5, nf, bw, false, false);                                  // G = dgrad (every channel)
-    // xc1 = sft1(x4), x4 = lrelu(conv4(buf[:, 0:nf+3g]))
-    if (split) K4_RDB_TRY(k4_sft_train_bwd_gx(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], 0.2f, p->gx4, nullptr, 0, fl, 1.f,
+    // xc1 = sft1(x4), x4 = lrelu(conv4(buf[:, 0:nf+3g])): the LeakyReLU backward in the SFT launch (grad_x_lrelu)
+    if (split) K4_RDB_TRY(k4_sft_train_bwd_gx(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], 0.2f, p->gx4, nullptr, 0, 1, 1.f,
                                               nullptr, 0.f, nullptr, nullptr, stream));
-    else if (defer) K4_RDB_TRY(k4_sft_train_bwd_main(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], p->sft1[4], p->sft1[5], p->sft1[6],
-                                                0.2f, p->gx4, p->gc_acc ? p->gc_acc : p->gc1, p->ws1, p->ws1_bytes, nullptr, 0, p->gc_acc != nullptr, fl, 1.f, stream));
     else K4_RDB_TRY(k4_sft_train_bwd_side(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], p->sft1[4], p->sft1[5], p->sft1[6],
-                                     0.2f, p->gx4, p->gc_acc ? p->gc_acc : p->gc1, p->gsft1[0], p->gsft1[1], p->gsft1[2], p->gsft1[3], p->gsft1[4], p->gsft1[5], p->gsft1[6], p->gsft1[7],
-                                     p->ws1, p->ws1_bytes, nullptr, 0, p->gc_acc != nullptr, fl, 1.f, p->side_stream, stream));
-    if (!fl) K4_RDB_TRY(k4_lrelu_bwd(p->gx4, g, p->x4, g, n, g, 0.2f, p->gx4, g, stream));
+                                         0.2f, p->gx4, p->gc_acc ? p->gc_acc : p->gc1, p->gsft1[0], p->gsft1[1], p->gsft1[2], p->gsft1[3], p->gsft1[4], p->gsft1[5], p->gsft1[6], p->gsft1[7],
+                                         p->ws1, p->ws1_bytes, nullptr, 0, p->gc_acc != nullptr, 1, 1.f, p->side_stream, stream));
     K4_RDB_WGRAD(nf + 3 * g, p->gx4, g, g, 3);
-    K4_RDB_DGRAD(3, p->gx4, g, nf + 3 * g, true, fl);                              // G[:, 0:nf+3g] += dgrad (+ the mask of x3's slice, its last 32 channels)
+    K4_RDB_DGRAD(3, p->gx4, g, nf + 3 * g, true, true);                            // G[:, 0:nf+3g] += dgrad (+ the mask of x3's slice, its last 32 channels)
     for (int k = 3; k >= 1; --k) {                                                  // x_k = lrelu(conv_k(buf[:, 0:off]))
         const int off = nf + (k - 1) * g;
-        if (!fl) K4_RDB_TRY(k4_lrelu_bwd(p->G + off, bw, p->buf + off, bw, n, g, 0.2f, p->G + off, bw, stream));
         K4_RDB_WGRAD(off, p->G + off, g, bw, k - 1);
-        K4_RDB_DGRAD(k - 1, p->G + off, bw, off, true, fl && k > 1);               // (k == 1 completes xc0's slice: sft0's output, no activation)
+        K4_RDB_DGRAD(k - 1, p->G + off, bw, off, true, k > 1);                     // (k == 1 completes xc0's slice: sft0's output, no activation)
     }
-    // gx0_add != NULL: gx0 = the gradient through sft0 + gx0_add (the block's skip connection: grad_out itself)
+    // gx0 = the gradient through sft0 + gx0_add (the block's skip connection: grad_out itself)
     if (split) K4_RDB_TRY(k4_sft_train_bwd_gx(p->t, nf, p->c, 32, p->G, bw, n, nf, p->sft0[0], p->sft0[1], p->sft0[2], p->sft0[3], 0.2f, p->gx0, p->gx0_add, nf, 0, 1.f,
                                               p->g5_next, 0.2f, p->gx0_add2, p->gx0_sum2, stream));
-    else if (defer) K4_RDB_TRY(k4_sft_train_bwd_main(p->t, nf, p->c, 32, p->G, bw, n, nf, p->sft0[0], p->sft0[1], p->sft0[2], p->sft0[3], p->sft0[4], p->sft0[5], p->sft0[6],
-                                                0.2f, p->gx0, p->gc_acc ? p->gc_acc : p->gc0, p->ws0, p->ws0_bytes, p->gx0_add, nf, p->gc_acc != nullptr, 0, 1.f, stream));
     else K4_RDB_TRY(k4_sft_train_bwd_side(p->t, nf, p->c, 32, p->G, bw, n, nf, p->sft0[0], p->sft0[1], p->sft0[2], p->sft0[3], p->sft0[4], p->sft0[5], p->sft0[6],
-                                     0.2f, p->gx0, p->gc_acc ? p->gc_acc : p->gc0, p->gsft0[0], p->gsft0[1], p->gsft0[2], p->gsft0[3], p->gsft0[4], p->gsft0[5], p->gsft0[6], p->gsft0[7],
-                                     p->ws0, p->ws0_bytes, p->gx0_add, nf, p->gc_acc != nullptr, 0, 1.f, p->side_stream, stream));
-    if (defer) {                                                                    // the block's side-stream work behind ONE fork (one event record, both streams wait for it)
-        K4_RDB_TRY(k4_wait_stream(side, main_s, split ? aux : nullptr));
+                                         0.2f, p->gx0, p->gc_acc ? p->gc_acc : p->gc0, p->gsft0[0], p->gsft0[1], p->gsft0[2], p->gsft0[3], p->gsft0[4], p->gsft0[5], p->gsft0[6], p->gsft0[7],
+                                         p->ws0, p->ws0_bytes, p->gx0_add, nf, p->gc_acc != nullptr, 0, 1.f, p->side_stream, stream));
+    if (split) {                                                                    // the block's side-stream work behind ONE fork (one event record, both streams wait for it)
+        K4_RDB_TRY(k4_wait_stream(side, main_s, aux));
         // aux_wgrad: conv1's weight gradient (the first piece of the span) runs on the third stream behind the SFT layers' deferred launches -- per block the
         // weight gradients' stream carried ~130 us of launches against ~70 us on the third stream and ~110 us on the chain: it had become the pace of the pass
-        const bool wg_aux = split && p->aux_wgrad != 0 && p->dwdb_span_floats > 0 && p->dwdb[0] == p->dwdb_span && p->dwdb[1] > p->dwdb[0] &&
-                            (p->dwdb[1] - p->dwdb[0]) < p->dwdb_span_floats;
+        const bool wg_aux = p->aux_wgrad != 0 && p->dwdb[0] == p->dwdb_span && p->dwdb[1] > p->dwdb[0] && (p->dwdb[1] - p->dwdb[0]) < p->dwdb_span_floats;
         const int64_t n_aux = wg_aux ? (int64_t)(p->dwdb[1] - p->dwdb[0]) : 0;
-        if (p->dwdb_span_floats > 0) K4_RDB_TRY(k4_zero_f32(p->dwdb_span + n_aux, p->dwdb_span_floats - n_aux, (void*)side));
+        K4_RDB_TRY(k4_zero_f32(p->dwdb_span + n_aux, p->dwdb_span_floats - n_aux, (void*)side));
         for (int q = 0; q < nwq; ++q) {
             if (wg_aux && wq[q].k == 0) continue;
-            if (p->dwdb_span_floats > 0) K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6_acc(p->buf, wq[q].cin, bw, wq[q].gy, wq[q].cout, wq[q].gys, 3, H, W, p->dwdb[wq[q].k], (void*)side));
-            else K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6(p->buf, wq[q].cin, bw, wq[q].gy, wq[q].cout, wq[q].gys, 3, H, W, p->dwdb[wq[q].k], (void*)side));
+            K4_RDB_TRY(k4_conv2d_wgrad_dbias_bf16x6_acc(p->buf, wq[q].cin, bw, wq[q].gy, wq[q].cout, wq[q].gys, 3, H, W, p->dwdb[wq[q].k], (void*)side));
         }
-        // split: what the chain did not wait for -- both SFT layers' hidden / condition gradients and partial sums, then their reductions -- on the third stream,
+        // what the chain did not wait for -- both SFT layers' hidden / condition gradients and partial sums, then their reductions -- on the third stream,
         // in the order the one-launch form adds into gc_acc (sft1, then sft0)
-        hipStream_t red = split ? aux : side;
-        if (split) K4_RDB_TRY(k4_sft_train_bwd_rest(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], p->sft1[4], p->sft1[5], p->sft1[6],
-                                                    0.2f, p->gc_acc, p->ws1, p->ws1_bytes, 1, 1.f, (void*)aux));
-        K4_RDB_TRY(k4_sft_train_reduce(p->ws1, n, g, p->gsft1[0], p->gsft1[1], p->gsft1[2], p->gsft1[3], p->gsft1[4], p->gsft1[5], p->gsft1[6], p->gsft1[7], (void*)red));
-        if (split) K4_RDB_TRY(k4_sft_train_bwd_rest(p->t, nf, p->c, 32, p->G, bw, n, nf, p->sft0[0], p->sft0[1], p->sft0[2], p->sft0[3], p->sft0[4], p->sft0[5], p->sft0[6],
-                                                    0.2f, p->gc_acc, p->ws0, p->ws0_bytes, 1, 1.f, (void*)aux));
-        K4_RDB_TRY(k4_sft_train_reduce(p->ws0, n, nf, p->gsft0[0], p->gsft0[1], p->gsft0[2], p->gsft0[3], p->gsft0[4], p->gsft0[5], p->gsft0[6], p->gsft0[7], (void*)red));
+        K4_RDB_TRY(k4_sft_train_bwd_rest(p->x4, g, p->c, 32, p->G + nf + 3 * g, bw, n, g, p->sft1[0], p->sft1[1], p->sft1[2], p->sft1[3], p->sft1[4], p->sft1[5], p->sft1[6],
+                                         0.2f, p->gc_acc, p->ws1, p->ws1_bytes, 1, 1.f, (void*)aux));
+        K4_RDB_TRY(k4_sft_train_reduce(p->ws1, n, g, p->gsft1[0], p->gsft1[1], p->gsft1[2], p->gsft1[3], p->gsft1[4], p->gsft1[5], p->gsft1[6], p->gsft1[7], (void*)aux));
+        K4_RDB_TRY(k4_sft_train_bwd_rest(p->t, nf, p->c, 32, p->G, bw, n, nf, p->sft0[0], p->sft0[1], p->sft0[2], p->sft0[3], p->sft0[4], p->sft0[5], p->sft0[6],
+                                         0.2f, p->gc_acc, p->ws0, p->ws0_bytes, 1, 1.f, (void*)aux));
+        K4_RDB_TRY(k4_sft_train_reduce(p->ws0, n, nf, p->gsft0[0], p->gsft0[1], p->gsft0[2], p->gsft0[3], p->gsft0[4], p->gsft0[5], p->gsft0[6], p->gsft0[7], (void*)aux));
         if (wg_aux) {
             K4_RDB_TRY(k4_zero_f32(p->dwdb_span, n_aux, (void*)aux));
             for (int q = 0; q < nwq; ++q)
@@ -1487,8 +1461,8 @@ join:
 #undef K4_RDB_WGRAD
 #undef K4_RDB_DGRAD
     {
-        // the wgrads are done before anything queued on `stream` after this call -- unless the caller joins itself, once (no_join; a failed launch joins anyway)
-        const int rj = (p->no_join && rc == 0) ? 0 : k4_wait_stream(main_s, side);
+        // the wgrads are done before anything queued on `stream` after this call -- unless the caller joins itself, once (split; a failed launch joins anyway)
+        const int rj = (split && rc == 0) ? 0 : k4_wait_stream(main_s, side);
         if (rc != 0 && split) (void)k4_wait_stream(main_s, aux);
         return rc != 0 ? rc : rj;
     }

@@ -18,8 +18,6 @@ lists into its dense gradient in RANK order, so the replicas hold bit-identical 
 with zero gradient" sees the union of the touched voxels).  Pure torch.distributed plumbing: RCCL on the GPUs, gloo in the
 CPU tests.
 """
-import os
-
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
@@ -131,8 +129,7 @@ class JointTrainer:
     """Optimizers + one-iteration method of the joint loop.  ``render_kwargs`` as run_sr.py:690-702 builds them
     (``render_depth=True``; ``rand_bkgd`` for LLFF); ``n_train_images`` = len(rays_o_tr), the TV weights' divisor (:1008-1011)."""
 
-    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, use_graph=None,
-                 near_clip=None):
+    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, near_clip=None):
         if cfg_train.weight_pcp > 0 or cfg_train.weight_gan > 0:
             raise NotImplementedError('perceptual / GAN losses (run_sr.py:934-957) are outside the hot-path scope (SURVEY.md 8)')
         if num_cond != 1 or dim_rend != 3:
@@ -147,9 +144,6 @@ class JointTrainer:
                                          'skip_zero_grad': False}])                                               # run_sr.py:665-667
         self.last_exchange = None
         self._after_march = None
-        # K4_TRAIN_GRAPH=1 / use_graph: the decoder's forward + backward of the full-size patch replayed as hipGraphs (lib/sr_train.GraphedDecoder)
-        self.use_graph = (os.environ.get('K4_TRAIN_GRAPH', '0') == '1') if use_graph is None else bool(use_graph)
-        self._graphed = None
 
     def rebuild_optimizer(self, global_step=0):
         """Re-create the marcher's optimizer after ``model.scale_volume_grid`` replaced the grid parameters (run_sr.py:812-818 does the
@@ -241,18 +235,7 @@ class JointTrainer:
         rgb_sr = self._decoder(rgb_cache, cond)                                          # run_sr.py:918
         return rr, rgb_sr, self.losses(rr, rgb_sr, target, target_4x, pr, pc, len(rays_o))
 
-    def _decoder(self, x, cond):
-        if self.use_graph and torch.is_grad_enabled() and x.requires_grad:
-            if self._graphed is None:
-                N_patch = self.cfg.N_rand // self.cfg.N_patch
-                if tuple(x.shape[2:]) == (N_patch, N_patch):                 # capture once, for the full-size patch (edge patches stay eager)
-                    try:
-                        self._graphed = sr_train.GraphedDecoder(self.net_sr, x.shape, cond.shape)
-                    except Exception as e:                                    # capture failed (e.g. an op that synchronises): stay eager
-                        print(f'JointTrainer: hipGraph capture of the decoder failed ({type(e).__name__}: {e}); using the eager path', flush=True)
-                        self.use_graph = False
-            if self._graphed is not None and self._graphed.matches(x, cond):
-                return self._graphed(x, cond)
+    def _decoder(self, x, cond):                                # (a method of its own: tools/joint_phase_events.py marks the phase around it)
         return self.net_sr(x, cond)
 
     def step(self, rays_o, rays_d, viewdirs, target, target_4x, pr, pc, global_step):

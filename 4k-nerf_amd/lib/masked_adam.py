@@ -47,14 +47,13 @@ def adam_upd_with_perlr(param, grad, exp_avg, exp_avg_sq, perlr, step, beta1, be
 
 def _side_stream(device):
     """The stream a large grid's update runs on: verified to run beside the current stream and the package's other side streams (_native.overlapping_stream)."""
-    return N.overlapping_stream(device, 'grid optimizer step', low_priority=_SIDE_LOW_PRIORITY)
+    return N.overlapping_stream(device, 'grid optimizer step')
 
 
 # The first part of a split grid step on at most this many workgroups (0: no cap).  It runs BESIDE the decoder's latency-bound kernels, which an HBM-saturating pass
 # slows by more than it saves (uncapped: 7.26 against 7.21 ms per joint iteration without the split); at 384-512 workgroups -- under two per CU, 2.1 ms for the LLFF
 # k0's 9.5 GB, beside the decoder's forward pass -- the iteration is 6.8-7.0 ms (profiles/r06_split_grid_step.md)
 _EARLY_WORKGROUPS = 448
-_SIDE_LOW_PRIORITY = False      # True: the grids' step stream at the device's lowest priority (A/B)
 
 
 _MULTI_BELOW = 1 << 20          # tensors smaller than this are updated through k4_adam_upd_multi (same arithmetic per element)

@@ -113,7 +113,7 @@ class DecoderProgram:
         self.main = N.stream().value or 0
         self.side = T._side_stream(dev)
         # a third stream for what the chain does not read of the SFT layers' backward (k4_sft_train_bwd_rest + reductions: condition gradient, parameter gradients)
-        self.aux = T._aux_stream(dev) if self.side is not None else None
+        self.aux = T._aux_stream(dev)
         f32 = dict(dtype=torch.float32, device=dev)
 
         def E(*shape):
@@ -249,13 +249,11 @@ class DecoderProgram:
             sb = scr.data_ptr()
             d.gx0, d.G, d.gx4, d.ws0, d.ws1, d.g5 = (sb + 4 * o for o in soff[:6])
             d.ws0_bytes, d.ws1_bytes = nb0, nb1
-            d.g5_from_gx0_add, d.fused_lrelu = 1, 1
             d.gc_acc = G['acc'].data_ptr()
             d.side_stream = self.side
-            d.no_join = int(self.side is not None)                # ONE join, behind the whole backward pass (_backward_calls): the buffers are this program's own
-            d.defer_side = int(self.side is not None)             # ... and ONE fork per block: every event record on the chain's stream costs ~7 us of the chain's time
-            d.aux_stream = self.aux                               # ... and only the grad_x part of the two SFT layers' backward on the chain
-            d.aux_wgrad = int(T._AUX_WGRAD and q > 0)             # ... one of the five weight gradients on the third stream (not in the last block of the pass: the chain joins that stream right after it)
+            d.aux_stream = self.aux                               # ONE fork per block, ONE join behind the whole backward pass (_backward_calls): the buffers are this
+                                                                  # program's own; only the grad_x part of the two SFT layers' backward on the chain
+            d.aux_wgrad = int(q > 0)                              # ... one of the five weight gradients on the third stream (not in the last block of the pass: the chain joins that stream right after it)
             self.scr.append(scr)
             self.desc.append(d)
         self.signature = signature(net)
@@ -267,21 +265,8 @@ class DecoderProgram:
                                               flags | pk.flags_extra | (CONV_SMALL if pk.k == 3 and not pk.flags_extra else 0), 0.2, None if res is None else N.f32(res), 0 if res is None else cout_stride,
                                               res_scale, None, 0, N.stream()), 'k4_conv2d_nhwc_bf16x6')
 
-    def _side_call(self, fn, aux=False):
-        """A launch that only produces parameter gradients (weight gradients, SFT reductions): queued for the side stream and issued by _flush_side behind a fork that
-        covers a whole section of the chain (a fork per launch put an event record -- ~7 us of the chain's time -- in front of every dgrad launch); without a side
-        stream it runs now, on the chain's stream.  aux: queued for the third stream instead (the tail of the pass: both streams share the last weight gradients)."""
-        if self.side is None:
-            fn(N.stream())
-        elif aux and self.aux is not None:
-            self._aux_q.append(fn)
-        else:
-            self._side_q.append(fn)
-
     def _flush_side(self, fork):
         """Issue the queued side-stream launches.  fork=False: the side stream already waits for everything queued so far (a dense block's call has just forked)."""
-        if self.side is None:
-            return
         for which, stream in (('_side_q', self.side), ('_aux_q', self.aux)):
             q = getattr(self, which)
             if not q:
@@ -294,11 +279,13 @@ class DecoderProgram:
             setattr(self, which, [])
 
     def _wgrad(self, mod, x, gy, H, W, name, aux=False):
-        """[dW | dbias] of `mod` into its piece of the flat buffer, on the side stream (_side_call)."""
+        """[dW | dbias] of `mod` into its piece of the flat buffer: a launch that only produces parameter gradients, queued for the side stream and issued by
+        _flush_side behind a fork that covers a whole section of the chain (a fork per launch put an event record -- ~7 us of the chain's time -- in front of
+        every dgrad launch).  aux: queued for the third stream instead (the tail of the pass: both streams share the last weight gradients)."""
         L = N.lib()
         cout, cin, k, _ = mod.weight.shape
         args = (N.f32(x), cin, cin, N.f32(gy), cout, cout, k, H, W, N.C.c_void_p(self.pg.data_ptr() + 4 * self.pg_off[name]))
-        self._side_call(lambda st: N.check(L.k4_conv2d_wgrad_dbias_bf16x6(*args, st), 'k4_conv2d_wgrad_dbias_bf16x6'), aux=aux)
+        (self._aux_q if aux else self._side_q).append(lambda st: N.check(L.k4_conv2d_wgrad_dbias_bf16x6(*args, st), 'k4_conv2d_wgrad_dbias_bf16x6'))
 
     def _lrelu_bwd(self, g, y):
         C = g.shape[2]
@@ -315,22 +302,16 @@ class DecoderProgram:
         pb = self.pg.data_ptr()
         L = N.lib()
         n = self.h * self.w
-        if self.aux is not None:              # the chain's launch writes grad_x only; the rest of the layer on the third stream (k4_rdb_train.aux_stream does the same inside a block)
-            # scaled_out: the g5 (= 0.2 grad_out) of the dense block that receives gx as its grad_out, written here instead of by a launch of its own
-            N.check(L.k4_sft_train_bwd_gx(None, C, N.f32(self.A['c']), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:4]], 0.2, N.f32(gx), None, 0, 0, float(gy_scale),
-                                          None if scaled_out is None else N.C.c_void_p(scaled_out), 0.2, None, None, N.stream()), 'k4_sft_train_bwd_gx')
-            # issued NOW, behind a fork of its own (six of these layers per pass): the third stream adds the layers' condition gradients in the chain's order
-            st = N.C.c_void_p(self.aux)
-            N.check(L.k4_side_wait_main(st, N.stream()), 'k4_side_wait_main')
-            N.check(L.k4_sft_train_bwd_rest(N.f32(x), C, N.f32(self.A['c']), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:7]], 0.2, N.f32(self.G['acc']),
-                                            N.f32(self.sft_ws[name]), self.sft_ws_bytes[C], 1, float(gy_scale), st), 'k4_sft_train_bwd_rest')
-            N.check(L.k4_sft_train_reduce(N.f32(self.sft_ws[name]), n, C, *[N.C.c_void_p(pb + 4 * o) for o in self.pg_off[name]], st), 'k4_sft_train_reduce')
-            return
-        N.check(L.k4_sft_train_bwd_main(N.f32(x), C, N.f32(self.A['c']), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:7]], 0.2,
-                                        N.f32(gx), N.f32(self.G['acc']), N.f32(self.sft_ws[name]), self.sft_ws_bytes[C], None, 0, 1, 0, float(gy_scale), N.stream()),
-                'k4_sft_train_bwd_main')
-        rargs = (N.f32(self.sft_ws[name]), n, C, *[N.C.c_void_p(pb + 4 * o) for o in self.pg_off[name]])
-        self._side_call(lambda st: N.check(L.k4_sft_train_reduce(*rargs, st), 'k4_sft_train_reduce'))
+        # the chain's launch writes grad_x only; the rest of the layer on the third stream (k4_rdb_train.aux_stream does the same inside a block).
+        # scaled_out: the g5 (= 0.2 grad_out) of the dense block that receives gx as its grad_out, written here instead of by a launch of its own
+        N.check(L.k4_sft_train_bwd_gx(None, C, N.f32(self.A['c']), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:4]], 0.2, N.f32(gx), None, 0, 0, float(gy_scale),
+                                      None if scaled_out is None else N.C.c_void_p(scaled_out), 0.2, None, None, N.stream()), 'k4_sft_train_bwd_gx')
+        # issued NOW, behind a fork of its own (six of these layers per pass): the third stream adds the layers' condition gradients in the chain's order
+        st = N.C.c_void_p(self.aux)
+        N.check(L.k4_side_wait_main(st, N.stream()), 'k4_side_wait_main')
+        N.check(L.k4_sft_train_bwd_rest(N.f32(x), C, N.f32(self.A['c']), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:7]], 0.2, N.f32(self.G['acc']),
+                                        N.f32(self.sft_ws[name]), self.sft_ws_bytes[C], 1, float(gy_scale), st), 'k4_sft_train_bwd_rest')
+        N.check(L.k4_sft_train_reduce(N.f32(self.sft_ws[name]), n, C, *[N.C.c_void_p(pb + 4 * o) for o in self.pg_off[name]], st), 'k4_sft_train_reduce')
 
     # ------------------------------------------------------------------------------------------------ the pass, call by call
     def _forward_calls(self):
@@ -401,9 +382,9 @@ class DecoderProgram:
         self._flush_side(fork=True)                                                # the high-resolution layers' weight gradients run beside the trunk's chain
         for b in range(nb - 1, -1, -1):
             rr = net.body[b]
-            fold = self.aux is not None          # the chain's grad_x launches also write what k_scale_f32 (a block's g5) and k4_add_f32 (the RRDB's input gradient) did
+            # the chain's grad_x launches also write a dense block's g5 (= 0.2 grad_out) and the RRDB's input gradient: no launches of their own for those
             self._sft_bwd(rr.sft0, A[f'o{3 * b + 2}'], g_body, G['o3'], f'sft{b}', 0.2,      # body_b = sft(o3) * 0.2 + body_{b-1}
-                          scaled_out=self.desc[3 * b + 2].g5 if fold else None)
+                          scaled_out=self.desc[3 * b + 2].g5)
             go = G['o3']
             # the RRDB's input reaches its first dense block and the skip connection: the sum of both gradients.  The first RRDB's input is `feat`,
             # which the long skip connection reads too: three addends, summed in the order the autograd engine received them (same roundings)
@@ -412,40 +393,30 @@ class DecoderProgram:
                 q = 3 * b + r
                 d = self.desc[q]
                 d.gx0_add = go.data_ptr()
-                if fold:
-                    d.g5_given = 1
-                    d.g5_next = self.desc[q - 1].g5 if r > 0 else None
-                    if r == 0 and b > 0:
-                        d.gx0_add2, d.gx0_sum2 = g_body.data_ptr(), g_other.data_ptr()
-                    elif r == 0:
-                        N.check(L.k4_add_f32(N.f32(G['bf']), N.f32(g_body), N.f32(g_other), n * nf, N.stream()), 'k4_add_f32')
-                        d.gx0_add2, d.gx0_sum2 = g_other.data_ptr(), G['feat'].data_ptr()
+                d.g5_next = self.desc[q - 1].g5 if r > 0 else None
+                if r == 0 and b > 0:
+                    d.gx0_add2, d.gx0_sum2 = g_body.data_ptr(), g_other.data_ptr()
+                elif r == 0:
+                    N.check(L.k4_add_f32(N.f32(G['bf']), N.f32(g_body), N.f32(g_other), n * nf, N.stream()), 'k4_add_f32')
+                    d.gx0_add2, d.gx0_sum2 = g_other.data_ptr(), G['feat'].data_ptr()
                 N.check(L.k4_rdb_train_bwd(N.C.byref(d), N.stream()), 'k4_rdb_train_bwd')
                 self._flush_side(fork=False)                                       # (the block's call ended with a fork: what was queued before it is covered)
                 go = self.scr[q][:n * nf].view(h, w, nf)                           # = go + the gradient through the block's sft0
-            if fold:
-                g_body = g_other
-            elif b > 0:
-                N.check(L.k4_add_f32(N.f32(go), N.f32(g_body), N.f32(g_other), n * nf, N.stream()), 'k4_add_f32')
-                g_body = g_other
-            else:
-                N.check(L.k4_add_f32(N.f32(G['bf']), N.f32(g_body), N.f32(g_other), n * nf, N.stream()), 'k4_add_f32')
-                N.check(L.k4_add_f32(N.f32(g_other), N.f32(go), N.f32(G['feat']), n * nf, N.stream()), 'k4_add_f32')
+            g_body = g_other
         if nb == 0:
             N.check(L.k4_add_f32(N.f32(G['bf']), N.f32(g_body), N.f32(G['feat']), n * nf, N.stream()), 'k4_add_f32')
         self._wgrad(net.conv_first, A['xi'], G['feat'], h, w, 'conv_first')
         # The tail of the pass.  Behind the last dense block the weight gradients' stream still holds that block's five launches; conv_first's joins them at once when the
         # block's closing fork covers G['feat'] (it does when the block's grad_x launch wrote it), and the CondNet's four are dealt to both side streams behind the closing fork:
         # the pass ends ~75 us earlier than with all nine in one queue behind the chain's last launch.
-        tail_split = self.aux is not None and nb > 0 and T._TAIL_SPLIT
+        tail_split = nb > 0
         if tail_split:
             self._flush_side(fork=False)
         if self.x_grad:
             cin = A['xi'].shape[2]
             self._conv(self.bw_(net.conv_first), G['feat'], nf, G['xi'], cin, cin, h, w)
         # CondNet: G['acc'] holds the sum over every SFT layer -- once the third stream has added the last of them
-        if self.aux is not None:
-            N.check(L.k4_main_wait_side(N.C.c_void_p(self.aux), N.stream()), 'k4_main_wait_side')
+        N.check(L.k4_main_wait_side(N.C.c_void_p(self.aux), N.stream()), 'k4_main_wait_side')
         cn = net.CondNet
         self._wgrad(cn[6], A['c3'], G['acc'], h, w, 'cn6')
         self._conv(self.bw_(cn[6]), G['acc'], 32, G['c3'], 64, 64, h, w)
@@ -461,10 +432,9 @@ class DecoderProgram:
             ncond = A['ci'].shape[2]
             self._conv(self.bw_(cn[0]), G['c1'], 64, G['ci'], ncond, ncond, h, w)
         self._flush_side(fork=True)
-        if self.side is not None:
-            N.check(L.k4_main_wait_side(N.C.c_void_p(self.side), N.stream()), 'k4_main_wait_side')      # the weight gradients are done before the optimizer reads them
-            if tail_split:
-                N.check(L.k4_main_wait_side(N.C.c_void_p(self.aux), N.stream()), 'k4_main_wait_side')
+        N.check(L.k4_main_wait_side(N.C.c_void_p(self.side), N.stream()), 'k4_main_wait_side')          # the weight gradients are done before the optimizer reads them
+        if tail_split:
+            N.check(L.k4_main_wait_side(N.C.c_void_p(self.aux), N.stream()), 'k4_main_wait_side')
 
     # ------------------------------------------------------------------------------------------------ entry points of the autograd node
     def run_forward(self, x, cond):

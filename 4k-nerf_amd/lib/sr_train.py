@@ -26,7 +26,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .. import _native as N
-from .sr_esrnet import _Packed, _PackPlan, SFTNet, EPI_LRELU, EPI_RES, CONV_SMALL
+from .sr_esrnet import _Packed, _PackPlan, SFTNet, EPI_LRELU, CONV_SMALL
 
 
 class _WeightCache:
@@ -35,7 +35,6 @@ class _WeightCache:
     def __init__(self):
         self._c = {}
         self._plan = None          # prepack(): (signature, _PackPlan, modules, [weight versions], [bias versions])
-        self.always = False        # True: pack on every call (hipGraph capture: the packing kernels must be part of the graph, see GraphedDecoder)
 
     @staticmethod
     def _key(kind, weight, bias):
@@ -46,13 +45,11 @@ class _WeightCache:
         slot = (kind, weight.data_ptr())
         if hit is not None and type(hit[0]) is int:       # an operand of the prepack plan: current iff prepack() saw these versions
             q, plan = hit[0], self._plan
-            if plan is not None and (self.always or (plan[3][q] == weight._version and (bias is None or plan[4][q] == bias._version))):
+            if plan is not None and plan[3][q] == weight._version and (bias is None or plan[4][q] == bias._version):
                 return hit[1]
             # stale plan operand (a step without prepack()): pack for this use under a SEPARATE key -- the plan's slot stays, so the
             # next prepack() brings the operand back onto the persistent buffers
             hit, slot = self._c.get(('stale',) + slot), ('stale',) + slot
-        if self.always:
-            return make()
         key = self._key(kind, weight, bias)
         if hit is None or hit[0] != key:
             hit = (key, make())
@@ -69,7 +66,7 @@ class _WeightCache:
     def prepack(self, convs, dgrad=True):
         """Pack every operand of `convs` (modules with .weight / .bias) that an optimizer step made stale, now, in ceil(n / 64) launches
         into buffers that persist (sr_esrnet._PackPlan) instead of one launch + two allocations per operand on first use.  The plan is
-        rebuilt when the module list or a parameter's storage changes; under ``always`` every call re-packs."""
+        rebuilt when the module list or a parameter's storage changes."""
         sig = (dgrad,) + tuple(m.weight.data_ptr() for m in convs)
         plan = self._plan
         if plan is None or plan[0] != sig:
@@ -91,7 +88,7 @@ class _WeightCache:
             plan = self._plan = [sig, pp, list(convs), None, None, slots]
         wv = [m.weight._version for m in convs]
         bv = [-1 if m.bias is None else m.bias._version for m in convs]
-        if self.always or wv != plan[3] or bv != plan[4]:
+        if wv != plan[3] or bv != plan[4]:
             plan[1].run()
             plan[3], plan[4] = wv, bv
 
@@ -188,7 +185,7 @@ class _CondFan(torch.autograd.Function):
 
 class K4SFTLayer(torch.autograd.Function):
     """SFTLayer (lib/sr_esrnet.py:112-123) of an NHWC image: ``x * (scale(cond) + 1) + shift(cond)`` with both 1x1-convolution pairs,
-    LeakyReLU and the modulation in ONE launch forward (k4_sft_train_fwd) and two backward (k4_sft_train_bwd: grad_x, grad_cond, the
+    LeakyReLU and the modulation in ONE launch forward (k4_sft_train_fwd) and two backward (k4_sft_train_bwd_ex: grad_x, grad_cond, the
     eight weight / bias gradients).  As four K4Conv2d Functions + elementwise autograd a layer was ~45 launches per iteration.
     `acc` (None | [H, W, 32]): the layer's condition gradient is ADDED to it and None returned for `cond` (see _CondFan).
     `res` (None | [H, W, C]), `res_scale`: the layer's output goes through ``* res_scale + res`` in the forward kernel's store (the RRDB's
@@ -244,49 +241,22 @@ class K4SFTLayer(torch.autograd.Function):
         return (gx, None if acc is not None else gc, None, g_res, None, *g)
 
 
-def _sft_bwd(x, x_stride, C, cond, gy, gy_off, gy_stride, n_pix, ws):
-    """k4_sft_train_bwd on channel windows: (grad_x [n_pix, C], grad_cond [n_pix, 32], the eight weight / bias gradients)."""
-    L = N.lib()
-    w0s, b0s, w1s, b1s, w0h, b0h, w1h, b1h = ws
-    gx = torch.empty([n_pix, C], dtype=torch.float32, device=x.device)
-    gc = torch.empty([n_pix, 32], dtype=torch.float32, device=x.device)
-    g = [torch.empty_like(t) for t in ws]
-    nbytes = int(L.k4_sft_train_bwd_workspace_bytes(n_pix, C))
-    wk = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device)
-    N.check(L.k4_sft_train_bwd(N.f32(x), x_stride, N.f32(cond), 32, N.C.c_void_p(gy.data_ptr() + 4 * gy_off), gy_stride, n_pix, C,
-                               N.f32(w0s), N.f32(b0s), N.f32(w1s), N.f32(b1s), N.f32(w0h), N.f32(b0h), N.f32(w1h), 0.2, N.f32(gx), N.f32(gc),
-                               *[N.f32(t) for t in g], N.f32(wk), nbytes, N.stream()), 'k4_sft_train_bwd')
-    return gx, gc, g
-
-
-_NATIVE_RDB = True      # False: a dense block's launches issued one by one from Python (A/B)
-_WGRAD_STREAM = True    # False: the block's weight gradients on the chain's own stream (A/B)
-_SIDE_LOW_PRIORITY = False      # True: the weight gradients' stream at the device's lowest priority (A/B: no effect)
-_FUSED_LRELU = True     # False: a dense block's four LeakyReLU backward passes as launches of their own (A/B, tests)
 _DIRECT_GRADS = os.environ.get('K4_TRAIN_DIRECT_GRADS', '1') != '0'  # 0: every parameter an autograd input of its Function (torch.autograd.grad, parameter hooks)
 _COND_ACC = True        # False: every SFT consumer returns its condition gradient, autograd adds them (A/B)
-_TAIL_SPLIT = True      # False: the last weight gradients of the backward pass (conv_first, CondNet) in one queue behind the chain's last launch (A/B)
-_AUX_WGRAD = True       # False: all five weight gradients of a dense block on the weight gradients' stream (A/B)
-_SFT_SPLIT = True       # False: the SFT layers' whole backward on the chain's stream, as one launch each (A/B, tests)
 _TAPE = os.environ.get('K4_TRAIN_TAPE', '1') != '0'     # 0: the decoder as ~20 autograd nodes per RRDB (below) instead of ONE node on two launch tapes (lib/sr_tape.py)
 
 
 def _side_stream(device):
     """The second HIP stream (per device) a dense block's weight-gradient launches go to (k4_rdb_train_bwd: forked / joined inside the call)."""
-    if not _WGRAD_STREAM:
-        return None
     # (one per MAIN stream -- callers on different streams do not share one -- and verified to run BESIDE it: _native.overlapping_stream)
-    st = N.overlapping_stream(device, 'decoder weight gradients', low_priority=_SIDE_LOW_PRIORITY)
-    return st.cuda_stream
+    return N.overlapping_stream(device, 'decoder weight gradients').cuda_stream
 
 
 def _aux_stream(device):
     """The third stream of the decoder's backward pass (lib/sr_tape.py): the SFT layers' deferred backward (k4_sft_train_bwd_rest) and their reductions.  It is
     the stream the dense total-variation term uses (lib/grid.py: that work is done long before the decoder's backward pass starts, and stream order keeps any
     overlap correct) -- main + weight gradients + grid optimizer step + this one are the four hardware queues a process gets (_native.overlapping_stream)."""
-    if not (_WGRAD_STREAM and _SFT_SPLIT):
-        return None
-    return N.overlapping_stream(device, 'dense total variation', low_priority=_SIDE_LOW_PRIORITY).cuda_stream
+    return N.overlapping_stream(device, 'dense total variation').cuda_stream
 
 
 def _hand_over_grads(params, grads):
@@ -367,7 +337,7 @@ class K4RDB(torch.autograd.Function):
         t, c = t.contiguous(), c.contiguous()
         H, W, nf = t.shape
         g = P[8].shape[0]
-        bw, n = nf + 4 * g, H * W
+        bw = nf + 4 * g
         assert c.shape == (H, W, 32) and len(P) == 26 and g == 32 and nf in (32, 64)
         assert acc is None or (acc.shape == c.shape and acc.is_contiguous() and acc.dtype == torch.float32)
         for q in P:
@@ -377,34 +347,19 @@ class K4RDB(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=t.device)
         buf, x4, out = torch.empty([H, W, bw], **f32), torch.empty([H, W, g], **f32), torch.empty([H, W, nf], **f32)
         ctx.acc = acc
-        if _NATIVE_RDB:                                   # the seven launches below, issued by ONE native call (include/k4nerf.h, k4_rdb_train)
-            d = _rdb_desc(t, c, buf, x4, P, H, W, nf, g)
-            d.out = out.data_ptr()
-            packs = [cache.fwd(P[8 + 2 * k], P[9 + 2 * k]) for k in range(5)]
-            for k, pk in enumerate(packs):
-                assert pk.mode == 'bf16x6' and pk.k == 3 and pk.flags_extra == 0
-                d.w_fwd[k], d.b_fwd[k] = pk.w.data_ptr(), pk.b.data_ptr()
-            N.check(L.k4_rdb_train_fwd(N.C.byref(d), N.stream()), 'k4_rdb_train_fwd')
-            if ctx.direct is not None:
-                ctx.save_for_backward(t, c, buf, x4)
-                ctx.P = P
-            else:
-                ctx.save_for_backward(t, c, buf, x4, *P)
-            ctx.cache, ctx.desc = cache, d                # the backward fills in its own fields of the same descriptor
-            return out
-        N.check(L.k4_sft_train_fwd(N.f32(t), nf, N.f32(c), 32, n, nf, *[N.f32(q) for q in P[0:8]], 0.2, N.f32(buf), bw, N.stream()), 'k4_sft_train_fwd')
-        for k in (1, 2, 3):
-            SFTNet._conv(cache.fwd(P[6 + 2 * k], P[7 + 2 * k]), buf, 0, bw, buf, nf + (k - 1) * g, bw, g, H, W, flags=EPI_LRELU)
-        SFTNet._conv(cache.fwd(P[14], P[15]), buf, 0, bw, x4, 0, g, g, H, W, flags=EPI_LRELU)
-        N.check(L.k4_sft_train_fwd(N.f32(x4), g, N.f32(c), 32, n, g, *[N.f32(q) for q in P[18:26]], 0.2,
-                                   N.C.c_void_p(buf.data_ptr() + 4 * (nf + 3 * g)), bw, N.stream()), 'k4_sft_train_fwd')
-        SFTNet._conv(cache.fwd(P[16], P[17]), buf, 0, bw, out, 0, nf, nf, H, W, flags=EPI_RES, res=(t, 0, nf, 0.2))
+        d = _rdb_desc(t, c, buf, x4, P, H, W, nf, g)                # seven launches, issued by ONE native call (include/k4nerf.h, k4_rdb_train)
+        d.out = out.data_ptr()
+        packs = [cache.fwd(P[8 + 2 * k], P[9 + 2 * k]) for k in range(5)]
+        for k, pk in enumerate(packs):
+            assert pk.mode == 'bf16x6' and pk.k == 3 and pk.flags_extra == 0
+            d.w_fwd[k], d.b_fwd[k] = pk.w.data_ptr(), pk.b.data_ptr()
+        N.check(L.k4_rdb_train_fwd(N.C.byref(d), N.stream()), 'k4_rdb_train_fwd')
         if ctx.direct is not None:
             ctx.save_for_backward(t, c, buf, x4)
             ctx.P = P
         else:
             ctx.save_for_backward(t, c, buf, x4, *P)
-        ctx.cache = cache
+        ctx.cache, ctx.desc = cache, d                    # the backward fills in its own fields of the same descriptor
         return out
 
     @staticmethod
@@ -416,76 +371,44 @@ class K4RDB(torch.autograd.Function):
         _check_acc(acc)
         H, W, nf = t.shape
         g = P[8].shape[0]
-        bw, n = nf + 4 * g, H * W
+        n = H * W
         go = go.contiguous().float()
         grads = [None] * 26
-        if _NATIVE_RDB:                                   # the 19 launches of the host form below, issued by ONE native call; the weight gradients on a second stream
-            L, dev = N.lib(), t.device
-            d = ctx.desc
-            order, sizes, offs, span, soff, nb0, nb1, shapes = _rdb_bwd_layout(P, n, nf, g, acc is None)
-            pg = torch.empty([offs[-1]], dtype=torch.float32, device=dev)
-            scr = torch.empty([soff[-1]], dtype=torch.float32, device=dev)
-            pb, sb = pg.data_ptr(), scr.data_ptr()
-            for q, (i, piece, shape) in enumerate(zip(order, pg.split(sizes), shapes)):
-                grads[i] = piece if shape is None else piece.view(shape)
-                ptr = pb + 4 * offs[q]
-                if q < 10:
-                    if q % 2 == 0:
-                        d.dwdb[q // 2] = ptr                                          # [dW | dbias] of conv q/2 + 1
-                elif q < 18:
-                    d.gsft0[q - 10] = ptr
-                else:
-                    d.gsft1[q - 18] = ptr
-            d.dwdb_span, d.dwdb_span_floats = pb, span
-            d.gx0_add = go.data_ptr()
-            d.gx0, d.G, d.gx4, d.ws0, d.ws1, d.g5 = (sb + 4 * o for o in soff[:6])
-            d.ws0_bytes, d.ws1_bytes = nb0, nb1
-            d.g5_from_gx0_add, d.fused_lrelu = 1, int(_FUSED_LRELU)          # g5 = 0.2 grad_out inside the call; the four LeakyReLU backward passes in epilogues
-            if acc is None:
-                d.gc0, d.gc1, d.gc_acc = sb + 4 * soff[6], sb + 4 * soff[7], None
+        # the block's 19 launches, issued by ONE native call; the weight gradients on a second stream
+        L, dev = N.lib(), t.device
+        d = ctx.desc
+        order, sizes, offs, span, soff, nb0, nb1, shapes = _rdb_bwd_layout(P, n, nf, g, acc is None)
+        pg = torch.empty([offs[-1]], dtype=torch.float32, device=dev)
+        scr = torch.empty([soff[-1]], dtype=torch.float32, device=dev)
+        pb, sb = pg.data_ptr(), scr.data_ptr()
+        for q, (i, piece, shape) in enumerate(zip(order, pg.split(sizes), shapes)):
+            grads[i] = piece if shape is None else piece.view(shape)
+            ptr = pb + 4 * offs[q]
+            if q < 10:
+                if q % 2 == 0:
+                    d.dwdb[q // 2] = ptr                                          # [dW | dbias] of conv q/2 + 1
+            elif q < 18:
+                d.gsft0[q - 10] = ptr
             else:
-                d.gc_acc = acc.data_ptr()
-            keep = []
-            for k in range(5):
-                pk = cache.bwd(P[8 + 2 * k])
-                assert pk.mode == 'bf16x6' and pk.k == 3 and pk.flags_extra == 0
-                d.w_bwd[k], d.b_bwd[k] = pk.w.data_ptr(), pk.b.data_ptr()
-                keep.append(pk)
-            d.side_stream = _side_stream(dev)
-            N.check(L.k4_rdb_train_bwd(N.C.byref(d), N.stream()), 'k4_rdb_train_bwd')
-            gt = scr[:n * nf].view(H, W, nf)                                          # = go + the gradient through sft0 (added in the kernel's store)
-            gc = None if acc is not None else (scr[soff[6]:soff[7]] + scr[soff[7]:soff[8]]).view(H, W, 32)
-            if ctx.direct is not None:
-                _hand_over_grads(ctx.direct, grads)
-                return gt, gc, None, None, None
-            return (gt, gc, None, None, *grads)
-
-        G = torch.empty([H, W, bw], dtype=torch.float32, device=t.device)
-
-        def accum(pk, src, s_off, s_stride, cout):                      # G[..., :cout] += dgrad: the output is its own residual
-            SFTNet._conv(pk, src, s_off, s_stride, G, 0, bw, cout, H, W, flags=EPI_RES, res=(G, 0, bw, 1.0))
-
-        # conv5: out = 0.2 conv5(buf) + t
-        g5 = go * 0.2
-        SFTNet._conv(cache.bwd(P[16]), g5, 0, nf, G, 0, bw, bw, H, W)                                                 # G = dgrad (every channel)
-        grads[16], grads[17] = _wgrad(buf, 0, bw, bw, g5, 0, nf, nf, 3, H, W, P[16].shape, True)
-        # xc1 = sft1(x4), x4 = lrelu(conv4(buf[:nf+3g]))
-        gx4, gc1, grads[18:26] = _sft_bwd(x4, g, g, c, G, nf + 3 * g, bw, n, P[18:26])
-        _lrelu_bwd(gx4, 0, g, x4, 0, g, n, g, gx4, 0, g)
-        cin4 = nf + 3 * g
-        accum(cache.bwd(P[14]), gx4, 0, g, cin4)                                                                      # G[:cin4] += dgrad
-        grads[14], grads[15] = _wgrad(buf, 0, cin4, bw, gx4, 0, g, g, 3, H, W, P[14].shape, True)
-        for k in (3, 2, 1):                                                                                         # x_k = lrelu(conv_k(buf[:off]))
-            off = nf + (k - 1) * g
-            _lrelu_bwd(G, off, bw, buf, off, bw, n, g, G, off, bw)
-            accum(cache.bwd(P[6 + 2 * k]), G, off, bw, off)
-            grads[6 + 2 * k], grads[7 + 2 * k] = _wgrad(buf, 0, off, bw, G, off, g, bw, 3, H, W, P[6 + 2 * k].shape, True)
-        gx0, gc0, grads[0:8] = _sft_bwd(t, nf, nf, c, G, 0, bw, n, P[0:8])                                            # xc0 = sft0(t)
-        gt = go + gx0.view(H, W, nf)
-        gc = (gc0 + gc1).view(H, W, 32)
-        if acc is not None:
-            acc.add_(gc)
-            gc = None
+                d.gsft1[q - 18] = ptr
+        d.dwdb_span, d.dwdb_span_floats = pb, span
+        d.gx0_add = go.data_ptr()                                                 # g5 = 0.2 grad_out is written inside the call
+        d.gx0, d.G, d.gx4, d.ws0, d.ws1, d.g5 = (sb + 4 * o for o in soff[:6])
+        d.ws0_bytes, d.ws1_bytes = nb0, nb1
+        if acc is None:
+            d.gc0, d.gc1, d.gc_acc = sb + 4 * soff[6], sb + 4 * soff[7], None
+        else:
+            d.gc_acc = acc.data_ptr()
+        keep = []
+        for k in range(5):
+            pk = cache.bwd(P[8 + 2 * k])
+            assert pk.mode == 'bf16x6' and pk.k == 3 and pk.flags_extra == 0
+            d.w_bwd[k], d.b_bwd[k] = pk.w.data_ptr(), pk.b.data_ptr()
+            keep.append(pk)
+        d.side_stream = _side_stream(dev)
+        N.check(L.k4_rdb_train_bwd(N.C.byref(d), N.stream()), 'k4_rdb_train_bwd')
+        gt = scr[:n * nf].view(H, W, nf)                                          # = go + the gradient through sft0 (added in the kernel's store)
+        gc = None if acc is not None else (scr[soff[6]:soff[7]] + scr[soff[7]:soff[8]]).view(H, W, 32)
         if ctx.direct is not None:
             _hand_over_grads(ctx.direct, grads)
             return gt, gc, None, None, None
@@ -524,7 +447,7 @@ def forward_train(net, x, cond):
     fused = os.environ.get('K4_TRAIN_SFT', 'fused') != 'convs'               # 'convs': one Function per convolution + elementwise autograd (A/B, tests)
     # The whole decoder as ONE autograd node whose forward and backward are launch tapes replayed by one native call each (lib/sr_tape.py): what the
     # direct gradient hand-over below needs (no parameter hooks, no graph capture), on the shapes the fused kernels cover.
-    if (fused and _TAPE and _DIRECT_GRADS and _NATIVE_RDB and _FUSED_LRELU and _COND_ACC and _TAP is None and x.is_cuda
+    if (fused and _TAPE and _DIRECT_GRADS and _COND_ACC and _TAP is None and x.is_cuda
             and not torch.cuda.is_current_stream_capturing() and not _params_hooked(net)):
         from . import sr_tape
         anchor = next((p for p in net.k4_parameters() if p.requires_grad), None)
@@ -606,41 +529,6 @@ def forward_train(net, x, cond):
         _TAP('conv_hr', None, None, hr)
     out = conv(net.conv_last, hr)
     return out.permute(2, 0, 1).unsqueeze(0)
-
-
-class GraphedDecoder:
-    """``forward_train`` + its backward for ONE input shape as two hipGraphs (``torch.cuda.make_graphed_callables``).
-
-    The decoder's training graph on a 64x64 patch is ~2500 launches of 4-30 us (229 convolutions x (pack, forward | pack, dgrad,
-    wgrad, dbias) + the elementwise glue): 25 of the joint iteration's 42 ms were host time spent issuing them.  Every launch goes
-    to torch's current stream and every buffer comes from torch's allocator, so the whole thing is capturable; the weight packers
-    are kernels (k4_pack_conv_weight_bf16x6) and run INSIDE the graphs (``_WeightCache.always``): a replay after an optimizer step
-    re-packs the updated weights.  Shapes other than the captured one fall back to the eager path (the caller keeps both)."""
-
-    def __init__(self, net, x_shape, cond_shape):
-        dev = next(net.parameters()).device
-        cache = net._k4.setdefault('train_cache', _WeightCache())
-
-        class _Fwd(torch.nn.Module):
-            def __init__(self, net):
-                super().__init__()
-                self.net = net
-
-            def forward(self, x, cond):
-                return forward_train(self.net, x, cond)
-        self.x_shape, self.cond_shape = tuple(x_shape), tuple(cond_shape)
-        sample = (torch.rand(self.x_shape, device=dev, requires_grad=True), torch.rand(self.cond_shape, device=dev))
-        cache.always = True
-        try:
-            self.fn = torch.cuda.make_graphed_callables(_Fwd(net), sample, allow_unused_input=True)    # scale 2 / dswise leave parameters unused
-        finally:
-            cache.always = False
-
-    def matches(self, x, cond):
-        return tuple(x.shape) == self.x_shape and tuple(cond.shape) == self.cond_shape and x.requires_grad and not cond.requires_grad
-
-    def __call__(self, x, cond):
-        return self.fn(x.contiguous(), cond.contiguous())
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -36,7 +36,8 @@ extern "C" {
 #define K4_ERR_BAD_ARG      10001   /* null pointer / non-positive size / unsupported combination */
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
-#define K4_ABI_VERSION      15      /* 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+/* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
+#define K4_ABI_VERSION      16      /* 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -511,7 +512,7 @@ int k4_lrelu_bwd(const float* grad, int32_t g_stride, const float* y, int32_t y_
                  float* out, int32_t out_stride, void* stream);
 
 /* A whole ResidualDenseBlock_SFT (lib/sr_esrnet.py:126-158) of the training graph issued by ONE call: the same launches, in the same order, as the
- * host issues through k4_sft_train_fwd / k4_conv2d_nhwc_bf16x6 / k4_conv2d_wgrad_dbias_bf16x6 / k4_lrelu_bwd / k4_sft_train_bwd (7 forward, 19 backward) --
+ * host would issue through k4_sft_train_fwd / k4_conv2d_nhwc_bf16x6 / k4_conv2d_wgrad_dbias_bf16x6_acc / k4_sft_train_bwd_ex (7 forward, 19 backward) --
  * the joint training iteration is paced by the host's ~900 Python-to-C calls (profiles/r04_train_wgrad_side_stream_slower.md), this removes ~390 of them.
  * Images are NHWC fp32; g = 32 growth channels, nf = 32 | 64; bw = nf + 4 g.
  *   forward : buf[:, 0:nf] = sft0(t, c); buf[:, nf+(k-1)g : nf+kg] = lrelu(conv_k(buf[:, 0:nf+(k-1)g])), k = 1..3; x4 = lrelu(conv4(buf[:, 0:nf+3g]));
@@ -535,28 +536,21 @@ typedef struct k4_rdb_train {
     float* gsft0[8]; float* gsft1[8];
     float* ws0; int64_t ws0_bytes; float* ws1; int64_t ws1_bytes;
     void* side_stream;
-    /* optional (all NULL / 0 = the behaviour above): */
-    float* gc_acc;                  /* both SFT layers ADD their condition gradient into this [n_pix][32] buffer (gc0 / gc1 unused): every SFT layer of the
-                                       decoder reads the same condition map, the sum over layers needs no kernels of its own */
-    const float* gx0_add;           /* gx0 = gradient of t through sft0 + gx0_add [n_pix][nf] (the block's skip connection: grad_out) */
+    float* gc_acc;                  /* NULL or: both SFT layers ADD their condition gradient into this [n_pix][32] buffer (gc0 / gc1 unused): every SFT layer of the
+                                       decoder reads the same condition map, the sum over layers needs no kernels of their own */
+    const float* gx0_add;           /* gx0 = gradient of t through sft0 + gx0_add [n_pix][nf] (the block's skip connection: grad_out); g5 = 0.2 gx0_add is WRITTEN by
+                                       the call (aux_stream NULL) or already there (aux_stream form: written by the producer of gx0_add, g5_next / grad_x_scaled) */
     float* dwdb_span; int64_t dwdb_span_floats;   /* the five dwdb buffers lie in this one span: ONE zero-fill for all of them */
-    int32_t fused_lrelu;            /* != 0: the four k4_lrelu_bwd launches run inside the epilogues of the launches in front of them (K4_EPI_LRELU_BWD, grad_x_lrelu):
-                                       same values */
-    int32_t g5_from_gx0_add;        /* != 0: g5 (a caller's [n_pix][nf] buffer) is WRITTEN here as 0.2 * gx0_add (= grad_out) */
-    int32_t no_join;                /* ABI 13, != 0: k4_rdb_train_bwd does NOT make `stream` wait for side_stream before it returns -- the caller joins once,
-                                       behind the last block (k4_main_wait_side), and keeps every buffer of the descriptor alive until then: with a join per
-                                       block the chain waited ~40 us at every block for the weight gradient it had forked last */
-    int32_t defer_side;             /* ABI 13, != 0 (with side_stream): the block's side-stream launches (zero-fill, five weight gradients, two SFT reductions) are issued at
-                                       the END of the block behind ONE fork instead of one fork per launch -- an event record on `stream` in front of every dgrad launch cost
-                                       ~7 us of the chain's time each.  Use with no_join (the weight gradients of a block then run beside the next block's chain). */
-    void* aux_stream;               /* ABI 14, != NULL (with defer_side, no_join, gc_acc): the chain runs only k4_sft_train_bwd_gx for the block's two SFT layers; the rest of
-                                       their backward (k4_sft_train_bwd_rest: condition gradient into gc_acc, partial sums) and the two reductions are issued on aux_stream
-                                       at the end of the block, behind the same event as the side stream's launches.  The caller joins aux_stream (k4_main_wait_side) before
-                                       the first reader of gc_acc and before the optimizer; the descriptor's buffers stay alive until then. */
-    float* g5_next;                 /* ABI 14 (aux_stream form): sft0's grad_x launch also writes 0.2 * gx0 here -- the g5 of the block that receives gx0 as its grad_out */
-    const float* gx0_add2; float* gx0_sum2;   /* ABI 14 (aux_stream form): ... and gx0_sum2 = gx0 + gx0_add2 (the RRDB's input gradient: last block's gx0 + the skip connection's) */
-    int32_t g5_given;               /* ABI 14, != 0 with g5_from_gx0_add: g5 already holds 0.2 * gx0_add (the producer of gx0_add wrote it: g5_next / grad_x_scaled) */
-    int32_t aux_wgrad;              /* ABI 14 (aux_stream form), != 0: conv1's weight gradient is issued on aux_stream (behind the SFT layers' deferred launches) instead of
+    void* aux_stream;               /* NULL: the form above.  != NULL (with side_stream, gc_acc; the launch tapes' form, lib/sr_tape.py): the block's side-stream launches
+                                       (zero-fill, weight gradients, SFT reductions) are issued at the END of the block behind ONE fork -- an event record on `stream` in
+                                       front of every dgrad launch cost ~7 us of the chain's time each -- and NOT joined: the caller joins side_stream and aux_stream once,
+                                       behind the last block (k4_main_wait_side), and keeps every buffer of the descriptor alive until then (a join per block made the
+                                       chain wait ~40 us at every block).  The chain runs only k4_sft_train_bwd_gx for the block's two SFT layers; the rest of their
+                                       backward (k4_sft_train_bwd_rest: condition gradient into gc_acc, partial sums) and the two reductions go to aux_stream behind the
+                                       same fork.  The caller joins aux_stream before the first reader of gc_acc. */
+    float* g5_next;                 /* (aux_stream form) sft0's grad_x launch also writes 0.2 * gx0 here -- the g5 of the block that receives gx0 as its grad_out */
+    const float* gx0_add2; float* gx0_sum2;   /* (aux_stream form) ... and gx0_sum2 = gx0 + gx0_add2 (the RRDB's input gradient: last block's gx0 + the skip connection's) */
+    int32_t aux_wgrad;              /* (aux_stream form) != 0: conv1's weight gradient is issued on aux_stream (behind the SFT layers' deferred launches) instead of
                                        side_stream: the two streams carry about the same time per block */
 } k4_rdb_train;
 int k4_rdb_train_fwd(const k4_rdb_train* p, void* stream);
@@ -694,13 +688,8 @@ int k4_sft_train_fwd_ex(const float* x, int32_t x_stride, const float* cond, int
                         const float* w0h, const float* b0h, const float* w1h, const float* b1h,
                         float slope, float* y, int32_t y_stride, const float* res, int32_t res_stride, float res_scale, void* stream);
 int64_t k4_sft_train_bwd_workspace_bytes(int64_t n_pix, int32_t channels);       /* < 0: unsupported channel count */
-int k4_sft_train_bwd(const float* x, int32_t x_stride, const float* cond, int32_t cond_stride, const float* grad_y, int32_t gy_stride,
-                     int64_t n_pix, int32_t channels,
-                     const float* w0s, const float* b0s, const float* w1s, const float* b1s, const float* w0h, const float* b0h, const float* w1h,
-                     float slope, float* grad_x, float* grad_cond,
-                     float* gw0s, float* gb0s, float* gw1s, float* gb1s, float* gw0h, float* gb0h, float* gw1h, float* gb1h,
-                     float* workspace, int64_t workspace_bytes, void* stream);
-/* The same with the two sums the training graph puts right behind it folded into the stores: grad_x = the layer's gradient + grad_x_add
+/* The backward (grad_x, grad_cond, the eight weight / bias gradients), with the two sums the training graph puts right behind it folded into the stores:
+ * grad_x = the layer's gradient + grad_x_add
  * ([n_pix][gxa_stride] rows; NULL = none) and, with accumulate_grad_cond != 0, grad_cond += the layer's gradient (the caller zeroes it once per
  * backward pass: every SFT layer of the decoder reads the same condition map).  grad_x_lrelu != 0: x is the OUTPUT of a LeakyReLU(slope) and
  * grad_x is the gradient in front of it: grad_x *= (x > 0 ? 1 : slope) (k4_lrelu_bwd folded in; before grad_x_add).  grad_y_scale: grad_y is multiplied by it as it is
@@ -719,7 +708,7 @@ int k4_sft_train_bwd_ex(const float* x, int32_t x_stride, const float* cond, int
  * AND is appended to the tape with a copy of its arguments (host structs and job arrays included); k4_tape_replay issues the recorded calls again
  * from C++, in order.  A call whose `stream` argument was `main_stream` runs on the replaying stream, a call placed on another stream (side-stream
  * weight gradients) stays there.  Recordable: k4_conv2d_nhwc_bf16x6, k4_conv2d_wgrad_bf16x6, k4_conv2d_wgrad_dbias_bf16x6(_acc), k4_conv2d_bias_grad,
- * k4_zero_f32, k4_pack_conv_weight_bf16x6(_multi), k4_lrelu_bwd, k4_sft_train_fwd(_ex), k4_sft_train_bwd(_ex), k4_rdb_train_fwd / _bwd (one entry
+ * k4_zero_f32, k4_pack_conv_weight_bf16x6(_multi), k4_lrelu_bwd, k4_sft_train_fwd(_ex), k4_sft_train_bwd_ex, k4_rdb_train_fwd / _bwd (one entry
  * each) and the five entry points below.  The caller keeps every buffer a tape names alive and in place; one recording per thread at a time
  * (k4_tape_begin returns NULL otherwise). */
 typedef struct k4_tape k4_tape;

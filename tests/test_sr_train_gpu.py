@@ -160,37 +160,6 @@ def test_direct_parameter_gradients_equal_the_autograd_edges(monkeypatch):
     assert max(_rel(a, b) for a, b in zip(on, off)) <= 5e-6        # (weight gradients: split-K atomics)
 
 
-def test_dense_block_backward_with_folded_leaky_relu_is_bit_identical(monkeypatch):
-    """k4_rdb_train_bwd with fused_lrelu: the block's four LeakyReLU backward passes run in the epilogues of the launches in front of them
-    (K4_EPI_LRELU_BWD in three dgrad accumulations, grad_x_lrelu in sft1's backward) instead of as k4_lrelu_bwd launches.  Same
-    arithmetic, same order: the gradients of the block's input and of the condition map (no atomics on that chain) must be bit-identical;
-    the weight gradients (split-K atomics) to rounding."""
-    g = torch.Generator().manual_seed(31)
-    blk = sr_esrnet.ResidualDenseBlock_SFT(64, 32)
-    with torch.no_grad():
-        for n, p in blk.named_parameters():
-            p.copy_(torch.randn(p.shape, generator=g) * (0.3 if 'SFT' in n else 1.5 / max(1, p[0].numel()) ** 0.5))
-    blk = blk.cuda()
-    H, W = 37, 45                                                   # ragged tiles: the kernels' general epilogue path as well as the fast one
-    t0, c0 = torch.randn([H, W, 64], generator=g).cuda(), torch.randn([H, W, 32], generator=g).cuda()
-    go = torch.randn([H, W, 64], generator=g).cuda()
-
-    def sp(layer):
-        return (layer.SFT_scale_conv0.weight, layer.SFT_scale_conv0.bias, layer.SFT_scale_conv1.weight, layer.SFT_scale_conv1.bias,
-                layer.SFT_shift_conv0.weight, layer.SFT_shift_conv0.bias, layer.SFT_shift_conv1.weight, layer.SFT_shift_conv1.bias)
-    convs = [q for m in (blk.conv1, blk.conv2, blk.conv3, blk.conv4, blk.conv5) for q in (m.weight, m.bias)]
-    res = []
-    for fused in (True, False):
-        monkeypatch.setattr(sr_train, '_FUSED_LRELU', fused)
-        blk.zero_grad(set_to_none=True)
-        t, c = t0.clone().requires_grad_(True), c0.clone().requires_grad_(True)
-        sr_train.K4RDB.apply(t, c, sr_train._WeightCache(), None, *sp(blk.sft0), *convs, *sp(blk.sft1)).backward(go)
-        res.append((t.grad.clone(), c.grad.clone(), [p.grad.clone() for p in blk.parameters()]))
-    (ta, ca, pa), (tb, cb, pb) = res
-    assert torch.equal(ta, tb) and torch.equal(ca, cb)
-    assert max(_rel(a, b) for a, b in zip(pa, pb)) <= 2e-6
-
-
 def test_training_step_updates_inference_path():
     """One optimizer step on the HIP training graph, then the no-grad inference kernels must see the new weights (packed-weight
     caches are keyed on parameter versions)."""
@@ -349,7 +318,7 @@ def test_multi_layer_weight_packer_is_bit_identical_to_single_launches():
 
 
 @pytest.mark.parametrize('use_acc', [False, True])
-@pytest.mark.parametrize('H,W', [(16, 24), (64, 64), (7, 13)])
+@pytest.mark.parametrize('H,W', [(16, 24), (64, 64), (7, 13), (37, 45)])
 def test_dense_block_function_matches_module_autograd(H, W, use_acc):
     """K4RDB (the ResidualDenseBlock with its two SFT layers as one autograd node: one block image, one gradient image, dgrads that
     accumulate in place) against fp64 autograd of the module (lib/sr_esrnet.py:126-158)."""
@@ -433,6 +402,7 @@ def test_decoder_tape_equals_the_per_block_graph(monkeypatch, cond_grad):
     assert len(progs) == 1 and len(progs[0][1]) == 1                       # one program, leased and released three times
     prog = progs[0][1][0]
     assert not prog.busy and len(prog.fwd_tape) > 20 and len(prog.bwd_tape) > 30
+    assert prog.aux is not None                                            # the SFT layers' backward split between the chain and a third stream
     net_b, hb = run(False)
     assert not any(isinstance(k, tuple) and k and k[0] == 'tape_programs' for k in net_b._k4)
     for it, ((oa, xa, ca, pa), (ob, xb, cb, pb)) in enumerate(zip(ht, hb)):
@@ -446,20 +416,22 @@ def test_decoder_tape_equals_the_per_block_graph(monkeypatch, cond_grad):
         assert max(_rel(pa[n], pb[n]) for n in pa) <= 5e-5, it
 
 
-def test_decoder_tape_replay_is_bit_identical_to_its_recording_pass():
+@pytest.mark.parametrize('cond_grad', [False, True])
+def test_decoder_tape_replay_is_bit_identical_to_its_recording_pass(cond_grad):
     """The same input through a fresh network (recording pass) and through one whose tapes already exist (replay): identical bits on every chain
-    without atomics."""
+    without atomics -- the condition gradient (summed by the third stream in the chain's order) included."""
     make, x0, c0, tgt = _tape_fixture(nb=1, h=16, w=24, seed=23)
     net = make()
     res = []
     for it in range(3):
-        x = x0.clone().requires_grad_(True)
+        x, c = x0.clone().requires_grad_(True), c0.clone().requires_grad_(cond_grad)
         net.zero_grad(set_to_none=True)
-        out = net(x, c0)
+        out = net(x, c)
         F.l1_loss(out, tgt).backward()
-        res.append((out.detach().clone(), x.grad.clone(), {n: p.grad.clone() for n, p in net.named_parameters()}))
-    for o, gx, pg in res[1:]:
+        res.append((out.detach().clone(), x.grad.clone(), {n: p.grad.clone() for n, p in net.named_parameters()}, c.grad.clone() if cond_grad else None))
+    for o, gx, pg, gc in res[1:]:
         assert torch.equal(o, res[0][0]) and torch.equal(gx, res[0][1])
+        assert gc is None or torch.equal(gc, res[0][3])
         for n in pg:
             if not _conv_like(n):
                 assert torch.equal(pg[n], res[0][2][n]), n
@@ -681,32 +653,3 @@ def test_sft_backward_in_two_launches_equals_the_one_launch_form(C, n, lrelu, ad
     assert L.k4_sft_train_bwd_gx(None, C, N.f32(cond), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:4]], 0.2, N.f32(gx_b), None, 0, 1, 1.0, *tail) != 0
     assert L.k4_sft_train_bwd_gx(None, C, N.f32(cond), 32, N.f32(gy), C, n, C, *[N.f32(p) for p in ps[:4]], 0.2, N.f32(gx_b), None, 0, 0, 1.0,
                                  None, 0.0, N.f32(add2), None, N.stream()) != 0                   # add2 without sum2
-
-
-def test_decoder_tape_with_the_sft_backward_on_a_third_stream_is_bit_identical(monkeypatch):
-    """lib/sr_tape.py with sr_train._SFT_SPLIT: the chain runs the grad_x launch of every SFT layer, the rest of the 36 layers' backward runs on a third
-    stream that adds the condition gradients in the chain's order -- output, input / condition gradients and the SFT layers' parameter gradients equal
-    the one-launch form's bit for bit, on the recording pass and on a replay; so are the by-products of the grad_x launches (a dense block's g5, the RRDB's
-    input gradient) that replace the k_scale_f32 / k4_add_f32 launches of the one-launch form."""
-    make, x0, c0, tgt = _tape_fixture()
-
-    def run(split):
-        monkeypatch.setattr(sr_train, '_SFT_SPLIT', split)
-        net = make()
-        hist = []
-        for it in range(2):
-            x, c = x0.clone().requires_grad_(True), c0.clone().requires_grad_(True)
-            net.zero_grad(set_to_none=True)
-            out = net(x, c)
-            F.l1_loss(out, tgt).backward()
-            torch.cuda.synchronize()
-            hist.append((out.detach().clone(), x.grad.clone(), c.grad.clone(), {n: p.grad.clone() for n, p in net.named_parameters()}))
-        prog = [v for k, v in net._k4.items() if isinstance(k, tuple) and k and k[0] == 'tape_programs'][0][1][0]
-        assert (prog.aux is not None) == split
-        return hist
-    for (oa, xa, ca, pa), (ob, xb, cb, pb) in zip(run(True), run(False)):
-        assert torch.equal(oa, ob) and torch.equal(xa, xb) and torch.equal(ca, cb)
-        for n in pa:
-            if not _conv_like(n):
-                assert torch.equal(pa[n], pb[n]), n
-            assert _rel(pa[n], pb[n]) <= 5e-5, n

@@ -395,38 +395,6 @@ def test_fused_joint_loss_terms_without_any_sample(monkeypatch):
             _close(a, b.cpu(), 'grad', rel=1e-6, abs_=1e-12)
 
 
-def test_graphed_decoder_matches_eager_and_sees_weight_updates():
-    """lib/sr_train.GraphedDecoder: SFTNet's training forward + backward captured as hipGraphs (the weight packers run inside them).
-    Replays must equal the eager path (same kernels; wgrad / dbias sum with atomics: 2e-5 relative) -- also after the weights changed."""
-    from nerf4k_amd.lib import sr_train
-    torch.manual_seed(11)
-    net = sr_esrnet.SFTNet(3, scale=4, num_feat=64, num_block=1, num_grow_ch=32, num_cond=1).cuda().train()
-    g = torch.Generator().manual_seed(12)
-    shape_x, shape_c = (1, 3, 16, 20), (1, 1, 16, 20)
-    graphed = sr_train.GraphedDecoder(net, shape_x, shape_c)
-    for it in range(3):
-        x0 = torch.rand(shape_x, generator=g).cuda()
-        cond = torch.rand(shape_c, generator=g).cuda()
-        tgt = torch.rand([1, 3, 64, 80], generator=g).cuda()
-        res = []
-        for fn in (lambda a, b: net(a, b), graphed):
-            net.zero_grad(set_to_none=True)
-            x = x0.clone().requires_grad_(True)
-            assert graphed.matches(x, cond)
-            with torch.enable_grad():
-                out = fn(x, cond)
-                torch.nn.functional.l1_loss(out, tgt).backward()
-            res.append((out.detach().clone(), x.grad.clone(), [p.grad.clone() for p in net.parameters()]))
-        (oe, xe, pe), (og, xg, pg) = res
-        assert torch.equal(oe, og), it
-        _close(xg, xe.cpu(), 'grad_x', rel=2e-5, abs_=1e-9)
-        for a, b in zip(pg, pe):
-            _close(a, b.cpu(), 'grad_param', rel=2e-5, abs_=1e-9)
-        with torch.no_grad():                                       # an "optimizer step": the next replay must pack the new weights
-            for p in net.parameters():
-                p.add_(torch.randn(p.shape, generator=g).cuda() * 0.02 * p.abs().mean())
-
-
 def test_rgbnet_layer_by_layer_path_and_rejected_shapes():
     """the layer-by-layer path (`rgbnet_sigmoid_layers`: stacks outside k4_rgbnet_fwd's shapes, inference only) against the
     module itself in fp64, including a depth-4 stack, odd widths and an input count that is not a multiple of 4 -- and the shapes that ARE

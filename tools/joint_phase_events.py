@@ -7,13 +7,9 @@ import numpy as np
 import torch
 import nerf4k_amd  # noqa: F401
 from nerf4k_amd import scene, joint_train
-from nerf4k_amd.lib import dvgo, sr_esrnet, sr_train, utils
+from nerf4k_amd.lib import dvgo, sr_esrnet, utils
 if os.environ.get('TOOL_SPLIT_STEP') == '0':                             # A/B: k0's step of the dense-TV iterations in one pass after the backward pass
     joint_train._SPLIT_GRID_STEP = False
-if os.environ.get('TOOL_SFT_SPLIT') == '0':                               # A/B: the SFT layers' whole backward on the chain (one launch each)
-    sr_train._SFT_SPLIT = False
-if os.environ.get('SIDE_PRIO') is not None and hasattr(sr_train, '_SIDE_LOW_PRIORITY'):
-    sr_train._SIDE_LOW_PRIORITY = os.environ['SIDE_PRIO'] != '0'
 dev = torch.device('cuda', 0)
 S0 = int(os.environ.get('STEP0', '0'))              # >= 10000: the iterations after tv_before (no TV, sparse grid gradients)
 ck = scene.make_llff_checkpoint()

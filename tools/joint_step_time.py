@@ -5,26 +5,11 @@ import torch
 import nerf4k_amd  # noqa: F401
 from nerf4k_amd import scene, joint_train
 from nerf4k_amd.lib import dvgo, sr_esrnet, utils
-if os.environ.get('TOOL_AUX_WGRAD') == '0':                              # A/B: all weight gradients on their own stream
-    from nerf4k_amd.lib import sr_train as _T3
-    _T3._AUX_WGRAD = False
-if os.environ.get('TOOL_TAIL_SPLIT') == '0':                             # A/B: the tail's weight gradients in one queue
-    from nerf4k_amd.lib import sr_train as _T4
-    _T4._TAIL_SPLIT = False
-if os.environ.get('TOOL_SIDE_LOW') == '1':                                # A/B: the decoder's side streams at the device's lowest priority
-    from nerf4k_amd.lib import sr_train as _T2
-    _T2._SIDE_LOW_PRIORITY = True
 if os.environ.get('TOOL_EARLY_WGS'):
     from nerf4k_amd.lib import masked_adam as _MA2
     _MA2._EARLY_WORKGROUPS = int(os.environ['TOOL_EARLY_WGS'])
-if os.environ.get('TOOL_ADAM_LOW') == '1':
-    from nerf4k_amd.lib import masked_adam as _MA
-    _MA._SIDE_LOW_PRIORITY = True
 if os.environ.get('TOOL_SPLIT_STEP') == '0':                             # A/B: k0's step of the dense-TV iterations in one pass after the backward pass
     joint_train._SPLIT_GRID_STEP = False
-if os.environ.get('TOOL_SFT_SPLIT') == '0':                               # A/B: the SFT layers' whole backward on the chain (one launch each)
-    from nerf4k_amd.lib import sr_train as _T
-    _T._SFT_SPLIT = False
 dev = torch.device('cuda', 0)
 ck = scene.make_llff_checkpoint()
 H, W = scene.LLFF_HW

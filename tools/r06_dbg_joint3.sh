@@ -13,8 +13,6 @@ for s in pre:
     with torch.cuda.stream(s):
         torch.zeros([1024], device=dev).add_(1)
 torch.cuda.synchronize()
-if os.environ.get('SIDE_PRIO') == '0':
-    sr_train._SIDE_LOW_PRIORITY = False
 ck = scene.make_llff_checkpoint()
 (H, W), K = scene.LLFF_HW, scene.LLFF_K
 poses = scene.llff_spiral_poses()

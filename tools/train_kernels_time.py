@@ -41,6 +41,10 @@ for C in (32, 64):
     gy = torch.randn([H * W, C], device=dev)
     ws = [torch.randn(s, device=dev) * 0.1 for s in ([32, 32], [32], [C, 32], [C], [32, 32], [32], [C, 32], [C])]
     y = torch.empty_like(x)
+    gx, gc, g = torch.empty_like(x), torch.empty_like(cond), [torch.empty_like(t) for t in ws]
+    nbytes = int(N.lib().k4_sft_train_bwd_workspace_bytes(H * W, C))
+    wk = torch.empty([nbytes // 4], device=dev)
     t_f = med(lambda: N.check(N.lib().k4_sft_train_fwd(N.f32(x), C, N.f32(cond), 32, H * W, C, *[N.f32(t) for t in ws], 0.2, N.f32(y), C, N.stream()), 'fwd'))
-    t_b = med(lambda: sr_train._sft_bwd(x, C, C, cond, gy, 0, C, H * W, ws))
+    t_b = med(lambda: N.check(N.lib().k4_sft_train_bwd_ex(N.f32(x), C, N.f32(cond), 32, N.f32(gy), C, H * W, C, *[N.f32(t) for t in ws[:7]], 0.2, N.f32(gx), N.f32(gc),
+                                                          *[N.f32(t) for t in g], N.f32(wk), nbytes, None, 0, 0, 0, 1.0, N.stream()), 'bwd'))
     print(f'sft C={C} {H}x{W}: forward {t_f:6.1f} us   backward (+ reduce) {t_b:6.1f} us')
