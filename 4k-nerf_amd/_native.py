@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 16
+K4_ABI_VERSION = 17
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -234,6 +234,17 @@ _EXTRA_SIGS = {
     'k4_streams_overlap': ([_P, _P], C.c_int),
     'k4_side_wait_main': ([_P, _P], C.c_int),
     'k4_main_wait_side': ([_P, _P], C.c_int),
+    'k4_disc_weight_bytes': ([_I32, _I32, _I32], C.c_int64),
+    'k4_disc_conv_s2': ([_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _F, _P], C.c_int),
+    'k4_disc_wgrad_workspace_bytes': ([_I32, _I32, _I32, _I32], C.c_int64),
+    'k4_disc_wgrad_s2': ([_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _I64, _P], C.c_int),
+    'k4_bilinear2x_nhwc': ([_P, _P, _I32, _I32, _I32, _P, _P], C.c_int),
+    'k4_bilinear2x_bwd_nhwc': ([_P, _I32, _I32, _I32, _P, _P], C.c_int),
+    'k4_sn_workspace_floats': ([_I32, _I32, _I32], C.c_int64),
+    'k4_sn_prepare': ([_P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P, _I32, _P], C.c_int),
+    'k4_sn_project_grad': ([_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P], C.c_int),
+    'k4_gan_loss_fwd': ([_P, _I64, _I32, _F, _P, _P], C.c_int),
+    'k4_gan_loss_bwd': ([_P, _I64, _I32, _F, _P, _P, _P], C.c_int),
 }
 
 

@@ -8,7 +8,9 @@ configs/llff/fern_lg_joint_l1.py) on this package's HIP training graph:
                   -> L1(LR) + L1(HR) + background entropy + distortion (k4_distortion_loss) + per-point rgb
                   -> backward -> [data parallel: gradient exchange] -> total-variation add-grad -> MaskedAdam x 2 -> lr decay
 
-The perceptual / GAN terms (weight_pcp, weight_gan; VGG and discriminator networks) are outside SURVEY.md 8 and raise.
+The adversarial term of the "+gan" recipes (run_sr.py:678-690, 916-957, 1016-1049) runs when a discriminator is handed in (``net_d``,
+lib/sr_unetdisc.UNetDiscriminatorSN): its generator loss joins ``total``, and after the two optimizer steps the discriminator takes its own
+step on the real patch and the detached decoder output.  The perceptual / style terms (weight_pcp, weight_style; VGG19) raise.
 
 Data parallelism (one 64x64 patch per rank, run_sr.py:829-835): the decoder's 15.8 MB of gradients, the rgbnet and every other
 small tensor travel in ONE flat all-reduce (lib/sr_train.allreduce_gradients); the voxel grids do not -- `k0.grid` is 1.36 GB
@@ -23,7 +25,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import _native as N
-from .lib import grid as G, sr_train, train_ops, utils
+from .lib import grid as G, sr_train, sr_unetdisc, train_ops, utils
 from .lib.masked_adam import MaskedAdam
 
 _ADAM_SIDE = True   # False: the k0 grid's optimizer step on the current stream (A/B, tests)
@@ -124,14 +126,25 @@ class JointCfg(dict):
         cfg.update(over)
         return cls(cfg)
 
+    @classmethod
+    def fern_lg_joint_l1_gan(cls, **over):
+        """configs/llff/fern_lg_joint_l1+gan.py: fern_lg_joint_l1 with weight_pcp=0.5, weight_gan=0.05, weight_style=0.2.  The preset carries the
+        perceptual / style weights as the configuration file states them; JointTrainer raises on them (VGG19 is not part of this package), so a
+        caller who wants the adversarial term alone passes ``weight_pcp=0, weight_style=0``."""
+        cfg = dict(weight_pcp=0.5, weight_gan=0.05, weight_style=0.2)
+        cfg.update(over)
+        return cls.fern_lg_joint_l1(**cfg)
+
 
 class JointTrainer:
     """Optimizers + one-iteration method of the joint loop.  ``render_kwargs`` as run_sr.py:690-702 builds them
     (``render_depth=True``; ``rand_bkgd`` for LLFF); ``n_train_images`` = len(rays_o_tr), the TV weights' divisor (:1008-1011)."""
 
-    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, near_clip=None):
-        if cfg_train.weight_pcp > 0 or cfg_train.weight_gan > 0:
-            raise NotImplementedError('perceptual / GAN losses (run_sr.py:934-957) are outside the hot-path scope (SURVEY.md 8)')
+    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, near_clip=None, net_d=None):
+        if cfg_train.weight_pcp > 0 or cfg_train.get('weight_style', 0) > 0:
+            raise NotImplementedError('perceptual / style losses (run_sr.py:934-945; basicsr PerceptualLoss on VGG19) are not provided')
+        if cfg_train.weight_gan > 0 and net_d is None:
+            raise NotImplementedError('weight_gan > 0 needs a discriminator: JointTrainer(..., net_d=sr_unetdisc.UNetDiscriminatorSN(3, 64)) (run_sr.py:679-690)')
         if num_cond != 1 or dim_rend != 3:
             raise NotImplementedError('joint step: num_cond=1 (depth condition), dim_rend=3 as configs/llff/fern_lg_joint_l1.py')
         self.model, self.net_sr, self.cfg, self.group = model, net_sr, cfg_train, group
@@ -144,6 +157,12 @@ class JointTrainer:
                                          'skip_zero_grad': False}])                                               # run_sr.py:665-667
         self.last_exchange = None
         self._after_march = None
+        # the adversarial term (run_sr.py:679-690); with weight_gan == 0 a discriminator handed in is ignored: the step is the one without it
+        self.net_d = net_d if cfg_train.weight_gan > 0 else None
+        self.optimizer_d = self.cri_gan = None
+        if self.net_d is not None:
+            self.cri_gan = sr_unetdisc.GANLoss(gan_type='vanilla', loss_weight=cfg_train.weight_gan)
+            self.optimizer_d = MaskedAdam([{'params': net_d.parameters(), 'lr': cfg_train.lrate_srnet, 'kname': 'd', 'skip_zero_grad': False}])
 
     def rebuild_optimizer(self, global_step=0):
         """Re-create the marcher's optimizer after ``model.scale_volume_grid`` replaced the grid parameters (run_sr.py:812-818 does the
@@ -233,7 +252,30 @@ class JointTrainer:
         rgb_cache = rr['rgb_feature'].reshape(1, pr, pc, -1).movedim(-1, 1)
         cond = rr['depth'].reshape(1, pr, pc, 1).movedim(-1, 1)                          # num_cond == 1 (run_sr.py:894-897)
         rgb_sr = self._decoder(rgb_cache, cond)                                          # run_sr.py:918
-        return rr, rgb_sr, self.losses(rr, rgb_sr, target, target_4x, pr, pc, len(rays_o))
+        ls = self.losses(rr, rgb_sr, target, target_4x, pr, pc, len(rays_o))
+        if self.net_d is not None:                               # generator phase (run_sr.py:920-922, 946-957): D frozen, one more summand of `total`
+            for p in self.net_d.parameters():
+                p.requires_grad = False
+            ls['g'] = self.cri_gan(self.net_d(rgb_sr), True, is_disc=False)
+            ls['total'] = ls['total'] + ls['g']
+        return rr, rgb_sr, ls
+
+    def _discriminator_step(self, rgb_sr, target_4x, pr, pc):
+        """run_sr.py:1019-1049: the discriminator's own iteration on the real patch and the detached decoder output."""
+        net_d, s = self.net_d, self.sr_ratio
+        for p in net_d.parameters():
+            p.requires_grad = True
+        self.optimizer_d.zero_grad()
+        rgb_hr = target_4x.detach().reshape(s * pr, s * pc, 3).movedim(-1, 0).unsqueeze(0).contiguous()
+        with torch.enable_grad():
+            d_real = self.cri_gan(net_d(rgb_hr), True, is_disc=True)
+            d_real.backward()
+            d_fake = self.cri_gan(net_d(rgb_sr.detach().clone()), False, is_disc=True)
+            d_fake.backward()
+        if _world(self.group) > 1 or (N.FORCE_COLLECTIVES and dist.is_initialized()):
+            sr_train.allreduce_gradients(list(net_d.parameters()), group=self.group)
+        self.optimizer_d.step()
+        return {'d_real': d_real.detach(), 'd_fake': d_fake.detach()}
 
     def _decoder(self, x, cond):                                # (a method of its own: tools/joint_phase_events.py marks the phase around it)
         return self.net_sr(x, cond)
@@ -332,8 +374,10 @@ class JointTrainer:
                     grid._k4_split = None
                     grid.__dict__.pop('_k4_split_flags', None)
         self.optimizer_sr.step()
+        if self.net_d is not None:
+            ls.update(self._discriminator_step(rgb_sr, target_4x, pr, pc))
         factor = 0.1 ** (1 / (cfg.lrate_decay * 1000))                                                           # run_sr.py:1052-1061
-        for opt in (self.optimizer, self.optimizer_sr):
+        for opt in (self.optimizer, self.optimizer_sr) + ((self.optimizer_d,) if self.optimizer_d is not None else ()):
             for pg in opt.param_groups:
                 pg['lr'] = pg['lr'] * factor
         return {k: v.detach() for k, v in ls.items()}

@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      16      /* 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      17      /* 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -770,6 +770,54 @@ int k4_sft_train_bwd_side(const float* x, int32_t x_stride, const float* cond, i
                           float* workspace, int64_t workspace_bytes,
                           const float* grad_x_add, int32_t gxa_stride, int32_t accumulate_grad_cond, int32_t grad_x_lrelu, float grad_y_scale,
                           void* side_stream, void* stream);
+
+/* ---- the U-Net discriminator of the "+gan" joint recipes (csrc/k4_disc.hip; lib/sr_unetdisc.py:7-62, run_sr.py:916-957, 1016-1049) ---------------
+ * All tensors NHWC fp32, one image.  Arithmetic of the convolutions: the exact 3-term bf16 splits of k4_conv2d_nhwc_bf16x6 (fp32-equivalent).
+ * Every entry point below is recordable on a launch tape; none uses float atomics (results do not depend on the run).
+ *
+ * k4_disc_conv_s2 (lib/sr_unetdisc.py:17-19, 35-37: nn.Conv2d(c, 2c, 4, 2, 1, bias=False) and autograd through it), by `mode`:
+ *   K4_DISC_CONV_FWD    y[Y][X][co] = act(sum x[2Y-1+dy][2X-1+dx][ci] W[co][ci][dy][dx]), x [Hin][Win][x_stride] (Hin, Win even), y [Hin/2][Win/2][y_stride];
+ *                       w_split = the forward operand of k4_sn_prepare (ksize 4); act = LeakyReLU(slope) when lrelu != 0
+ *   K4_DISC_CONV_DGRAD  the input gradient: x = dY [Hin][Win] with cin = the layer's cout channels, y = dX [2 Hin][2 Win] with cout = the layer's cin
+ *                       channels, four phases of 2x2 taps; w_split = the K4_DISC_PACK_T operand of k4_sn_prepare (ksize 4)
+ *   K4_DISC_CONV_DGRAD3 the input gradient of a 3x3 stride-1 pad-1 layer of ANY width (lib/sr_unetdisc.py:21: conv4 has 8*num_feat inputs, more
+ *                       than k4_conv_weight_bf16x6_bytes admits as outputs): x = dY, y = dX, both [Hin][Win]; w_split = the K4_DISC_PACK_T operand (ksize 3)
+ *   cin % 8 == 0, x 16-byte aligned with x_stride % 4 == 0 (K4_ERR_UNSUPPORTED otherwise).  Operand size: k4_disc_weight_bytes(outputs, inputs, ksize) =
+ *   [ceil(inputs/16)][3 terms][ksize^2][2][32*ceil(outputs/32)][8] bf16 -- for ksize 3 the layout of k4_conv_weight_bf16x6_bytes, without its width limit.
+ * k4_disc_wgrad_s2: dw [cout][cin][4][4] (overwritten) = sum_p gy[p][co] x[2p-1+(dy,dx)][ci]; x [H][W][x_stride], gy [H/2][W/2][gy_stride]; split-K partial sums go to
+ *   `workspace` (k4_disc_wgrad_workspace_bytes) and are added in band order. */
+#define K4_DISC_CONV_FWD    0
+#define K4_DISC_CONV_DGRAD  1
+#define K4_DISC_CONV_DGRAD3 2
+#define K4_DISC_PACK_FLIP   1      /* v = W[c][n][taps-1-tap]: the dgrad operand of k4_conv2d_nhwc_bf16x6 (form 1 of k4_pack_conv_weight_bf16x6) */
+#define K4_DISC_PACK_T      4      /* v = W[c][n][tap]: the operand of K4_DISC_CONV_DGRAD / _DGRAD3 */
+int64_t k4_disc_weight_bytes(int32_t cout, int32_t cin, int32_t ksize);
+int k4_disc_conv_s2(const float* x, int32_t cin, int32_t x_stride, int32_t Hin, int32_t Win, const void* w_split,
+                    float* y, int32_t cout, int32_t y_stride, int32_t mode, int32_t lrelu, float slope, void* stream);
+int64_t k4_disc_wgrad_workspace_bytes(int32_t cin, int32_t cout, int32_t H, int32_t W);
+int k4_disc_wgrad_s2(const float* x, int32_t cin, int32_t x_stride, int32_t H, int32_t W, const float* gy, int32_t cout, int32_t gy_stride,
+                     float* dw, float* workspace, int64_t workspace_bytes, void* stream);
+/* F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) (lib/sr_unetdisc.py:40, 45, 50), channels % 4 == 0, 16-byte aligned:
+ *   k4_bilinear2x_nhwc     : y [2H][2W][C] = resample(x + add) (add == NULL: of x; the skip sums of :43-44, :48-49 in the same pass)
+ *   k4_bilinear2x_bwd_nhwc : grad_x [H][W][C] = the transpose applied to grad_y [2H][2W][C] (a gather: each input row is read by at most four output rows) */
+int k4_bilinear2x_nhwc(const float* x, const float* add, int32_t H, int32_t W, int32_t channels, float* y, void* stream);
+int k4_bilinear2x_bwd_nhwc(const float* grad_y, int32_t H, int32_t W, int32_t channels, float* grad_x, void* stream);
+/* torch.nn.utils.spectral_norm as lib/sr_unetdisc.py:17-27 applies it (n_power_iterations=1, eps=1e-12), Wm = weight_orig [cout][cin*ksize^2], ksize 3 | 4:
+ *   train != 0: v <- normalize(Wm^T u), u <- normalize(Wm v) in place (x / max(|x|_2, eps));  sigma[0] = u . (Wm v)  (train == 0: with u, v as stored)
+ *   w_fwd (may be NULL with w_bwd): weight_orig / sigma packed as the forward operand, k4_disc_weight_bytes(cout, cin, ksize) bytes
+ *   w_bwd (may be NULL): ... as the input-gradient operand in `bwd_form` (K4_DISC_PACK_FLIP | K4_DISC_PACK_T), k4_disc_weight_bytes(cin, cout, ksize) bytes
+ *   workspace: k4_sn_workspace_floats(cout, cin, ksize) floats.  One call per layer (four launches).
+ * k4_sn_project_grad: out = g / sigma - (<g, weight_orig> / sigma^2) outer(u, v), the gradient of weight_orig / sigma(weight_orig) with u, v constant
+ *   (torch/nn/utils/spectral_norm.py computes sigma under autograd with u, v detached); g, out [cout][K]; out must not alias g. */
+int64_t k4_sn_workspace_floats(int32_t cout, int32_t cin, int32_t ksize);
+int k4_sn_prepare(const float* weight_orig, float* u, float* v, int32_t cout, int32_t cin, int32_t ksize, int32_t train, float eps,
+                  float* sigma, float* workspace, void* w_fwd, void* w_bwd, int32_t bwd_form, void* stream);
+int k4_sn_project_grad(const float* g, const float* weight_orig, const float* u, const float* v, const float* sigma, int32_t cout, int32_t K,
+                       float* workspace, float* out, void* stream);
+/* basicsr.losses.GANLoss(gan_type='vanilla') on logits (run_sr.py:941-944, 1031-1046) = BCEWithLogitsLoss against all ones (target_is_real) / all zeros:
+ *   loss[0] = scale * mean(softplus(target_is_real ? -x : x));   grad_logits = grad_loss[0] (NULL: 1) * scale / n * d softplus.  One launch each. */
+int k4_gan_loss_fwd(const float* logits, int64_t n, int32_t target_is_real, float scale, float* loss, void* stream);
+int k4_gan_loss_bwd(const float* logits, int64_t n, int32_t target_is_real, float scale, const float* grad_loss, float* grad_logits, void* stream);
 
 #ifdef __cplusplus
 }
