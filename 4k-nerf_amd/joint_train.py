@@ -41,6 +41,12 @@ def _world(group):
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
 
 
+def _exchange_runs(group):
+    """Does a gradient exchange run this iteration?  In a job of several ranks -- and in the one-rank RCCL smoke test (_native.FORCE_COLLECTIVES).  THE predicate: the
+    routes that keep a grid's gradient out of a dense ``.grad`` (JointTrainer.step) are taken only when it says no, and every exchange runs only when it says yes."""
+    return sr_train.collectives_run(_world(group))
+
+
 def touched_voxels(g, cap=None):
     """Sorted int32 indices of the columns of g [C, V] with a non-zero entry.  On the GPU: one pass of k4_touched_voxels over the gradient
     (no [C, V] boolean temporary -- 340 MB next to the 1.36 GB k0 gradient -- and one host synchronisation, for the count)."""
@@ -65,7 +71,7 @@ def sparse_grad_allreduce(params, group=None, average=True):
     world = _world(group)
     stats = {'world': world, 'bytes_gathered': 0, 'touched': []}
     params = [p for p in params if p.requires_grad]
-    if world == 1 and not (N.FORCE_COLLECTIVES and dist.is_initialized()):
+    if not _exchange_runs(group):
         return stats
     for p in params:
         C = p.shape[1] if p.dim() == 5 else 1
@@ -99,7 +105,7 @@ def sparse_grad_allreduce(params, group=None, average=True):
 
 def exchange_gradients(model, net_sr, group=None):
     """Data-parallel gradient exchange of the joint step: big grids sparse, everything else in one dense bucket."""
-    if _world(group) == 1 and not (N.FORCE_COLLECTIVES and dist.is_initialized()):
+    if not _exchange_runs(group):
         return {'world': 1}
     everything = [p for p in list(model.parameters()) + list(net_sr.parameters()) if p.requires_grad]
     big = [p for p in everything if p.numel() >= SPARSE_MIN_NUMEL and p.dim() == 5]
@@ -175,7 +181,7 @@ class JointTrainer:
         """Write the dense TV term ahead of the backward pass?  Only while TV is dense, and only in a single-process job: under data parallelism (a group of
         its own OR the default process group -- ``self.group`` is None for both that and no job at all) the exchange between backward and TV sends the
         touched voxels, which a dense seed would make all of them (3.6 GB per rank instead of a few MB)."""
-        return _TV_SEED and _world(self.group) == 1 and global_step < self.cfg.tv_dense_before
+        return _TV_SEED and not _exchange_runs(self.group) and global_step < self.cfg.tv_dense_before
 
     def _sparse_grid_owners(self):
         """The grids whose gradient may stay in the scatter's scratch image this iteration: multi-channel DenseGrids stepped by MaskedAdam on the side stream
@@ -272,7 +278,7 @@ class JointTrainer:
             d_real.backward()
             d_fake = self.cri_gan(net_d(rgb_sr.detach().clone()), False, is_disc=True)
             d_fake.backward()
-        if _world(self.group) > 1 or (N.FORCE_COLLECTIVES and dist.is_initialized()):
+        if _exchange_runs(self.group):
             sr_train.allreduce_gradients(list(net_d.parameters()), group=self.group)
         self.optimizer_d.step()
         return {'d_real': d_real.detach(), 'd_fake': d_fake.detach()}
@@ -284,79 +290,53 @@ class JointTrainer:
         """One iteration (run_sr.py:869-1014,1052-1061).  Returns the dict of loss tensors (detached)."""
         cfg = self.cfg
         tv_now = cfg.tv_after < global_step < cfg.tv_before and global_step % cfg.tv_every == 0                 # run_sr.py:1005-1011
-        # DENSE total variation does not look at the gradient: its term is written ahead of the backward pass (side stream) into the buffer
-        # the grid lookups' backward accumulates into -- the same sum with a third of the memory traffic, and none of it at the end of the
-        # iteration where the next iteration's sample selection waits (lib/grid.py total_variation_seed_grad).  Not under data parallelism:
-        # the gradient exchange between backward and TV sends the TOUCHED voxels, which a dense seed would make all of them.
+        # Where each grid's gradient goes this iteration (lib/grid.GridGrad; a grid that is not armed takes the reference's form: a dense `.grad` from zeros).
+        # 'dense' + seed: DENSE total variation does not look at the gradient, so its term is written ahead of the backward pass (side stream) into the buffer the
+        #   lookups' backward accumulates into -- the same sum with a third of the memory traffic, and none of it at the end of the iteration where the next iteration's
+        #   sample selection waits.
+        # 'split' + seed: ... and a grid MaskedAdam can step from the scratch image is stepped in two exact parts: every voxel the scatter cannot touch right after the
+        #   marcher's forward pass (beside the decoder's passes), the touched ones after the backward pass -- the dense pass over k0 (1.8 ms) no longer sits between
+        #   this iteration's backward pass and the next iteration's lookup.
+        # 'sparse': without TV (after tv_before: 290,000 of fern_lg_joint_l1's 300,000 iterations) the lookups' backward is the only contribution to k0's gradient and
+        #   MaskedAdam skips voxels without one: the backward stops after its scatter and the optimizer updates the touched voxels from there -- no dense 1.36 GB gradient.
+        # All three only when no gradient exchange runs: it reads the dense gradient and sends the TOUCHED voxels, which a dense seed would make all of them.
         seed_tv = tv_now and self._dense_tv_ahead(global_step)
-        seeded = []
-        # Without TV (after tv_before: 290,000 of fern_lg_joint_l1's 300,000 iterations) the lookups' backward is the only contribution to k0's gradient and
-        # MaskedAdam skips voxels without one: the backward stops after its scatter and the optimizer updates the touched voxels from the scratch image
-        # (lib/grid.DenseGrid._k4_sparse_grad, MaskedAdam._sparse_step) -- no dense 1.36 GB gradient per iteration.  Single process only: the data-parallel
-        # exchange reads the dense gradient.
-        sparse = self._sparse_grid_owners() if (_SPARSE_GRID_GRAD and not tv_now and _world(self.group) == 1) else []
-        for grid in sparse:
-            grid._k4_sparse_grad = True
-        if seed_tv:
-            for weight, grid, fn in ((cfg.weight_tv_density, getattr(self.model, 'density', None), self.model.density_total_variation_add_grad),
-                                     (cfg.weight_tv_k0, getattr(self.model, 'k0', None), self.model.k0_total_variation_add_grad)):
-                if weight > 0 and hasattr(grid, 'finish_grad_seed') and grid.grid.requires_grad:
-                    fn(weight / self.n_train_images, 'seed')
-                    seeded.append(grid)
-        # ... and a grid whose gradient is that term + what its lookups' backward scatters is stepped in two exact parts: every voxel the scatter cannot touch right after
-        # the forward pass (beside the decoder's passes), the touched ones after the backward pass (MaskedAdam.early_step) -- the dense pass over k0 (1.8 ms) no longer
-        # sits between this iteration's backward pass and the next iteration's lookup
-        split = [g for g in self._sparse_grid_owners() if g in seeded] if (_SPLIT_GRID_STEP and seed_tv) else []
-        for grid in split:
-            flags = grid.__dict__.get('_k4_split_flags')
-            if flags is None or flags.numel() != grid.grid[0, 0].numel() or flags.device != grid.grid.device:
-                flags = grid.__dict__['_k4_split_flags'] = torch.zeros([grid.grid[0, 0].numel()], dtype=torch.uint8, device=grid.grid.device)
-            grid._k4_split = {'flags': flags}
-        done = False
+        armed, seeded = [], []
 
-        def early():                                             # between the marcher's forward pass and the decoder's: the lookups' points are known
-            for grid in split:
-                seed, ev = grid._k4_seed
-                if self.optimizer.early_step(grid, seed, ev):
-                    grid._k4_seed = None                         # consumed: the backward pass leaves its sums in the scratch image
-                else:
-                    grid._k4_split = None                        # one-pass step after all
-                    grid.__dict__.pop('_k4_split_flags', None)
+        def arm(grid, route):
+            armed.append(grid)
+            grid.grad_route.arm(route)
         try:
+            if seed_tv:
+                owners = self._sparse_grid_owners() if _SPLIT_GRID_STEP else []
+                for weight, grid, fn in ((cfg.weight_tv_density, getattr(self.model, 'density', None), self.model.density_total_variation_add_grad),
+                                         (cfg.weight_tv_k0, getattr(self.model, 'k0', None), self.model.k0_total_variation_add_grad)):
+                    if weight > 0 and hasattr(grid, 'grad_route') and grid.grid.requires_grad:
+                        arm(grid, 'split' if grid in owners else 'dense')
+                        fn(weight / self.n_train_images, 'seed')
+                        seeded.append(grid)
+            elif _SPARSE_GRID_GRAD and not tv_now and not _exchange_runs(self.group):
+                for grid in self._sparse_grid_owners():
+                    arm(grid, 'sparse')
+            split = [g for g in seeded if g in owners] if seed_tv else []
             with torch.enable_grad():
                 if split:
                     # (zero_grad makes the current stream wait for a grid's pending update: in front of the first part, not behind it; its place relative to the
                     # forward pass changes nothing -- run_sr.py:961-962 clears the gradients between the loss terms and the backward pass (:1003))
                     self.optimizer.zero_grad(set_to_none=True)
                     self.optimizer_sr.zero_grad(set_to_none=True)
-                    self._after_march = early
-                try:
-                    rr, rgb_sr, ls = self.forward(rays_o, rays_d, viewdirs, target, target_4x, pr, pc, global_step)
-                finally:
-                    self._after_march = None
+                    # between the marcher's forward pass and the decoder's the lookups' points are known: the first part of the split step
+                    self._after_march = lambda: [g.grad_route.first_part(self.optimizer) for g in split]
+                rr, rgb_sr, ls = self.forward(rays_o, rays_d, viewdirs, target, target_4x, pr, pc, global_step)
+                self._after_march = None
                 if hasattr(self.model, '_k4_params_ready'):
                     self.model._k4_params_ready()                # (a forward that never read k0: its pending update still precedes what follows)
                 if not split:
                     self.optimizer.zero_grad(set_to_none=True)
                     self.optimizer_sr.zero_grad(set_to_none=True)
                 ls['total'].backward()
-            for grid in seeded:
-                grid.finish_grad_seed()
-            done = True
-        finally:
-            for grid in sparse:
-                grid._k4_sparse_grad = False
-                if not done:
-                    G.discard_pending_grad(grid)
-            if not done:                # forward / loss / backward raised (e.g. an out-of-memory batch the caller skips): a parked seed must not
-                for grid in seeded:     # reach a LATER iteration's gradient -- it holds a TV term of parameters that iteration no longer has
-                    grid._k4_seed = None
-                for grid in split:      # (a split step's first part stays applied -- those voxels' step of this iteration; flags and scratch image start afresh)
-                    G.discard_pending_grad(grid)
-                    grid._k4_split = None
-                    grid.__dict__.pop('_k4_split_flags', None)
-        stepped = False
-        try:
+            for grid in armed:
+                grid.grad_route.close()
             self.last_exchange = exchange_gradients(self.model, self.net_sr, self.group)
             if tv_now:
                 if cfg.weight_tv_density > 0 and getattr(self.model, 'density', None) not in seeded:
@@ -364,15 +344,12 @@ class JointTrainer:
                 if cfg.weight_tv_k0 > 0 and getattr(self.model, 'k0', None) not in seeded:
                     self.model.k0_total_variation_add_grad(cfg.weight_tv_k0 / self.n_train_images, global_step < cfg.tv_dense_before)
             self.optimizer.step()
-            stepped = True
         finally:
-            if not stepped:             # sums a scatter-only backward left in the scratch image must not be added to by the next iteration's
-                for grid in sparse + split:
-                    G.discard_pending_grad(grid)
-            for grid in split:
-                if grid._k4_split is not None:                   # (the second part did not run)
-                    grid._k4_split = None
-                    grid.__dict__.pop('_k4_split_flags', None)
+            # The one clean-up.  After a finished iteration this only disarms.  After one that raised (e.g. an out-of-memory batch the caller skips) nothing of it
+            # reaches a later one: parked seeds and pending sums are dropped, a split step whose first part ran is completed from the seed (GridGrad.abort)
+            self._after_march = None
+            for grid in armed:
+                grid.grad_route.abort()
         self.optimizer_sr.step()
         if self.net_d is not None:
             ls.update(self._discriminator_step(rgb_sr, target_4x, pr, pc))

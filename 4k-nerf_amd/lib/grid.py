@@ -32,36 +32,53 @@ class GridSample3D(torch.autograd.Function):
     def forward(ctx, grid, pts, xyz_min, xyz_max, owner=None):
         ctx.save_for_backward(pts, xyz_min, xyz_max)
         ctx.grid_shape = tuple(grid.shape)
-        ctx.owner = owner                                  # the DenseGrid: its backward may find a pre-seeded gradient buffer there
+        ctx.owner = owner                                  # the DenseGrid: its gradient route (GridGrad) says where this backward leaves the gradient
         return _grid_sample_fwd(grid.detach().contiguous(), pts, xyz_min, xyz_max)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         pts, xyz_min, xyz_max = ctx.saved_tensors
-        _, C_, X, Y, Z = ctx.grid_shape
-        owner = ctx.owner
-        split = owner is not None and owner._k4_split is not None and owner._k4_split.get('early', False)
-        if split:
-            # MaskedAdam has stepped every voxel this scatter cannot touch already (early_step): the sums stay in the scratch image for the second part
-            if not grid_sample_3d_backward_scatter(grad_out.float().contiguous(), C_, X, Y, Z, pts, xyz_min, xyz_max):
-                raise N.K4Error('GridSample3D.backward: the scratch image of a grid whose step was split is gone')
-            owner._k4_sparse_pending = True
-            return None, None, None, None, None
-        if owner is not None and owner._k4_sparse_grad and owner._k4_seed is None:
-            # the trainer consumes this gradient where the scatter leaves it (MaskedAdam -> k4_masked_adam_upd_sparse_cl): no dense tensor, `.grad` stays None
-            if grid_sample_3d_backward_scatter(grad_out.float().contiguous(), C_, X, Y, Z, pts, xyz_min, xyz_max):
-                owner._k4_sparse_pending = True
-                return None, None, None, None, None
-        gg = ctx.owner._take_grad_seed(ctx.grid_shape, grad_out.device) if ctx.owner is not None else None
-        if gg is None:
-            gg = torch.zeros(ctx.grid_shape, dtype=torch.float32, device=grad_out.device)
         go = grad_out.float().contiguous()
-        grid_sample_3d_backward(go, C_, X, Y, Z, pts, xyz_min, xyz_max, gg)
+        if ctx.owner is not None:
+            return ctx.owner.grad_route.backward(go, ctx.grid_shape, pts, xyz_min, xyz_max), None, None, None, None
+        gg = torch.zeros(ctx.grid_shape, dtype=torch.float32, device=go.device)
+        grid_sample_3d_backward(go, *ctx.grid_shape[1:], pts, xyz_min, xyz_max, gg)
         return gg, None, None, None, None
 
 
-_GSB_WS = {}          # device -> [(C, X, Y, Z), all-zero workspace of k4_grid_sample_3d_backward_cl, event of its last use]; one grid shape per device
+class _ScratchImage:
+    """One device's workspace of k4_grid_sample_3d_backward_cl ([voxel][C] fp32 sums + a flag byte per voxel: as large as the gradient).  It is all-zero
+    while `holder` is None.  From the first scatter that leaves sums in it until they are consumed (in-place optimizer step, sweep) or discarded, `holder`
+    is the GridGrad they belong to, and ``_scratch_image`` hands the image to nobody else."""
+    __slots__ = ('shape', 'ws', 'event', 'holder')
+
+    def __init__(self, shape, ws):
+        self.shape, self.ws, self.event, self.holder = shape, ws, None, None
+
+    def run(self, launch, stream=None):
+        """ONE buffer per device: `stream` (default: the current one) waits for the image's last use, `launch()` is issued, and its completion is the new
+        last use (-> that event).  A launch that raises drops the image -- it may hold half-written sums; the next use allocates a cleared one."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.ws.device)
+        if self.event is not None:
+            st.wait_event(self.event)
+        self.ws.record_stream(st)
+        try:
+            launch()
+        except Exception:
+            self.drop()
+            raise
+        self.event = torch.cuda.Event()
+        self.event.record(st)
+        return self.event
+
+    def drop(self):
+        self.holder = None
+        if _GSB_WS.get(self.ws.device) is self:
+            del _GSB_WS[self.ws.device]
+
+
+_GSB_WS = {}          # device -> _ScratchImage; one grid shape per device
 
 
 def release_grid_sample_workspace(device=None):
@@ -73,94 +90,41 @@ def release_grid_sample_workspace(device=None):
 GSB_CHANNEL_LAST = True
 
 
-def _gsb_workspace(device, C_, X, Y, Z):
-    """The device's cleared scratch image for this grid shape ([shape, int32 tensor, event of its last use]) or None (one channel, switched off, out of memory)."""
+def _who(route):
+    return 'a call without an owning grid' if route is None else f'DenseGrid({route.owner.extra_repr()}) at {id(route.owner):#x}'
+
+
+def _scratch_image(device, C_, X, Y, Z, taker=None):
+    """The device's scratch image for this grid shape, allocated (cleared) when missing or of another shape, or None (one channel, switched off, out of
+    memory).  `taker`: the GridGrad that asks (None: an ownerless dense call).  While the image holds a grid's pending sums only that grid gets it:
+    anybody else would sweep them into a gradient of its own (same shape) or free them (another shape)."""
     nbytes = int(N.lib().k4_grid_sample_3d_backward_workspace_bytes(C_, X, Y, Z)) if GSB_CHANNEL_LAST else -1
     if nbytes <= 0:
         return None
-    hit = _GSB_WS.get(device)
-    if hit is None or hit[0] != (C_, X, Y, Z):
+    img = _GSB_WS.get(device)
+    if img is not None and img.holder is not None and img.holder is not taker:
+        raise N.K4Error(f'grid_sample_3d backward for {_who(taker)}: the scratch image holds the pending gradient of {_who(img.holder)} '
+                        '(step or sweep that grid first)')
+    if img is None or img.shape != (C_, X, Y, Z):
         _GSB_WS.pop(device, None)
         try:
-            hit = _GSB_WS[device] = [(C_, X, Y, Z), torch.zeros([nbytes // 4], dtype=torch.int32, device=device), None]
+            img = _GSB_WS[device] = _ScratchImage((C_, X, Y, Z), torch.zeros([nbytes // 4], dtype=torch.int32, device=device))
         except torch.OutOfMemoryError:
             return None
-    return hit
+    return img
 
 
-def grid_sample_3d_backward_scatter(go, C_, X, Y, Z, pts, xyz_min, xyz_max):
-    """The scatter half of ``grid_sample_3d_backward``: the touched voxels' sums stay in the device's scratch image (added to what an earlier scatter left
-    there) until ``sweep_pending_grad`` moves them into a dense gradient or MaskedAdam consumes them in place.  -> False when there is no scratch image for
-    this grid (the caller takes the dense path)."""
-    hit = _gsb_workspace(go.device, C_, X, Y, Z)
-    if hit is None:
-        return False
-    n = pts.shape[0]
-    if n == 0:
-        return True
-    ws, cur = hit[1], torch.cuda.current_stream(go.device)
-    if hit[2] is not None:
-        cur.wait_event(hit[2])
-    ws.record_stream(cur)
-    try:
-        N.check(N.lib().k4_grid_sample_3d_backward_cl_scatter(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.ptr(ws), N.stream()),
-                'grid_sample_3d_backward_cl_scatter')
-    except Exception:
-        _GSB_WS.pop(go.device, None)
-        raise
-    hit[2] = torch.cuda.Event()
-    hit[2].record(cur)
-    return True
-
-
-def sweep_pending_grad(owner):
-    """Move the sums a scatter-only backward left in the scratch image into ``owner.grid.grad`` (created when missing): the dense gradient after all."""
-    owner._k4_sparse_pending = False
-    g = owner.grid
-    _, C_, X, Y, Z = g.shape
-    hit = _GSB_WS.get(g.device)
-    if hit is None or hit[0] != (C_, X, Y, Z):
-        raise N.K4Error('sweep_pending_grad: the scratch image of the pending gradient is gone')
-    if g.grad is None:
-        g.grad = torch.zeros_like(g, memory_format=torch.contiguous_format)
-    cur = torch.cuda.current_stream(g.device)
-    if hit[2] is not None:
-        cur.wait_event(hit[2])
-    hit[1].record_stream(cur)
-    N.check(N.lib().k4_grid_sample_3d_backward_cl_sweep(C_, X, Y, Z, N.ptr(hit[1]), N.f32(g.grad), N.stream()), 'grid_sample_3d_backward_cl_sweep')
-    hit[2] = torch.cuda.Event()
-    hit[2].record(cur)
-
-
-def discard_pending_grad(owner):
-    """Forget a scatter-only backward's sums (an iteration the caller gives up on): the scratch image is dropped, the next use allocates a cleared one."""
-    if owner._k4_sparse_pending:
-        owner._k4_sparse_pending = False
-        _GSB_WS.pop(owner.grid.device, None)
-
-
-def grid_sample_3d_backward(go, C_, X, Y, Z, pts, xyz_min, xyz_max, gg):
+def grid_sample_3d_backward(go, C_, X, Y, Z, pts, xyz_min, xyz_max, gg, taker=None):
     """gg [1|-, C, X, Y, Z] += d(trilinear lookup)/d(grid) for grad_out `go` [n, C] at `pts` [n, 3].  More than one channel: through the
     channel-last scratch image (k4_grid_sample_3d_backward_cl; the workspace, as large as the gradient, is allocated and cleared once
     per device and grid shape and kept -- GSB_CHANNEL_LAST = False (module attribute: bench A/B) or an allocation failure selects the channel-major atomic scatter).
-    The workspace must be all-zero on entry and is left all-zero by the sweep; it is ONE buffer per device, so a use on another HIP
-    stream waits for the previous use (event), and a failed launch drops it (the next call allocates a cleared one)."""
+    The image must be all-zero on entry (K4Error while it holds another grid's pending sums) and is left all-zero by the sweep."""
     L = N.lib()
     n = pts.shape[0]
-    hit = _gsb_workspace(go.device, C_, X, Y, Z) if n > 0 else None
-    if hit is not None:
-        ws, cur = hit[1], torch.cuda.current_stream(go.device)
-        if hit[2] is not None:
-            cur.wait_event(hit[2])                     # scatter + sweep of the previous call (possibly on another stream) have finished
-        ws.record_stream(cur)
-        try:
-            N.check(L.k4_grid_sample_3d_backward_cl(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.f32(gg), N.ptr(ws),
-                                                    N.stream()), 'grid_sample_3d_backward_cl')
-        except Exception:
-            _GSB_WS.pop(go.device, None)               # scatter done but sweep not: the image may hold non-zero sums
-            raise
-        hit[2] = torch.cuda.Event()
-        hit[2].record(cur)
+    img = _scratch_image(go.device, C_, X, Y, Z, taker) if n > 0 else None
+    if img is not None:
+        img.run(lambda: N.check(L.k4_grid_sample_3d_backward_cl(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.f32(gg), N.ptr(img.ws),
+                                                                 N.stream()), 'grid_sample_3d_backward_cl'))
     else:
         N.check(L.k4_grid_sample_3d_backward(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.f32(gg), N.stream()),
                 'grid_sample_3d_backward')
@@ -194,6 +158,175 @@ def _vec3(v):
     return torch.Tensor(v)
 
 
+class GridGrad:
+    """Where one DenseGrid's gradient of the current training iteration is, and how it reaches the optimizer (``DenseGrid.grad_route``; the trainer arms it per
+    iteration, lib/masked_adam.MaskedAdam consumes it; nobody else touches the fields).
+
+        idle --arm('dense' | 'sparse' | 'split')--> armed            (a seed -- the dense TV term written ahead, park_seed -- may be parked in any state)
+        armed 'split' --lookup under autograd--> corners flagged      (k4_grid_flag_corners: the voxels the backward will touch)
+        armed 'split' --first_part(optimizer)--> early                (every unflagged voxel stepped from the seed; lookups under autograd now raise)
+        backward:  'sparse' without a seed, or early: the scatter's sums stay in the device's scratch image, which this object then holds;
+                   otherwise a dense gradient (zeros or the seed, + scatter + sweep) is returned to autograd
+        close():   a seed no backward consumed becomes (or is added to) ``.grad``
+        optimizer: image() + consumed() around its in-place step / sweep() into a dense ``.grad``
+        abort():   from any state back to idle; nothing of this iteration reaches the next one
+    """
+
+    def __init__(self, owner):
+        self.owner = owner
+        self.route = None           # None: idle (a backward then takes the dense form)
+        self.seed = None            # (buffer, event of its completion)
+        self.early = None           # first part of a split step done: (optimizer, seed buffer, step count, (beta1, beta2, lr, eps))
+        self.sums = False           # this iteration's scatter sums are in the scratch image
+        self.flags = None           # split route: uint8 [X*Y*Z], all-zero between iterations and reused across them
+        self.flagged = False        # ... a lookup of this iteration wrote into them
+
+    idle = property(lambda self: self.route is None and self.seed is None and self.early is None and not self.sums)
+    pending = property(lambda self: self.sums or self.early is not None)         # the optimizer has an in-place step (or a sweep) to do
+
+    def arm(self, route):
+        if self.route is not None:
+            raise N.K4Error(f'GridGrad.arm({route!r}): still armed ({self.route!r}) -- the previous iteration was neither finished nor aborted')
+        if route not in ('dense', 'sparse', 'split'):
+            raise ValueError(f'GridGrad.arm: unknown route {route!r}')
+        if route == 'split':
+            g = self.owner.grid
+            if self.flags is None or self.flags.numel() != g[0, 0].numel() or self.flags.device != g.device:
+                self.flags = torch.zeros([g[0, 0].numel()], dtype=torch.uint8, device=g.device)
+        self.route = route
+
+    def lookup_flags(self):
+        """DenseGrid.forward under autograd: the flags this lookup's corners go into, or None."""
+        if self.route != 'split':
+            return None
+        if self.early is not None:
+            raise N.K4Error('DenseGrid.forward: a lookup under autograd after the first part of the split optimizer step')
+        self.flagged = True
+        return self.flags
+
+    def first_part(self, optimizer):
+        """Between the marcher's forward pass and the decoder's: ``optimizer.early_step`` steps every voxel no lookup flagged; refused -> the one-pass step."""
+        if self.route == 'split' and (self.seed is None or not optimizer.early_step(self.owner, *self.seed)):
+            self.route, self.flags, self.flagged = 'dense', None, False
+
+    def first_part_done(self, optimizer, seed, step, hyper):
+        """(MaskedAdam.early_step) the seed is consumed; the second part runs even if no backward pass reaches the grid (its flagged voxels: seed alone)."""
+        self.early, self.seed = (optimizer, seed, step, hyper), None
+
+    def split_flags(self):
+        """(MaskedAdam.early_step) the flags of a grid armed 'split' whose first part has not run, else None."""
+        return self.flags if self.route == 'split' and self.early is None else None
+
+    def split_part(self):
+        """(MaskedAdam) after the first part of a split step: (flags, seed, step count, hyper-parameters) for the second, else None."""
+        return (self.flags,) + self.early[1:] if self.early is not None else None
+
+    # ---- the dense TV term BEFORE the backward pass (no reference counterpart; joint_train.JointTrainer.step) ----
+    # The reference adds the term after backward (run_sr.py:1005-1011): zero-fill the gradient (4 B / voxel), scatter, then read grad + param
+    # and write grad (12 B) -- on the 339 M-float LLFF k0 that is 1.1 ms at the END of the iteration, where the next iteration's sample
+    # selection (a device-to-host read) waits for it.  Dense mode does not look at the gradient, so the term can be WRITTEN into a fresh
+    # buffer first (8 B / voxel, on a side stream under the iteration's host-paced phases) and the lookup's backward accumulates into
+    # that buffer instead of into zeros: grad = term + scatter, the same sum.
+    def park_seed(self, wx, wy, wz):
+        owner = self.owner
+        cur = torch.cuda.current_stream(owner.grid.device)
+        seed = torch.empty_like(owner.grid.data, memory_format=torch.contiguous_format)
+        side = _tv_stream(owner.grid.device)
+        side.wait_stream(cur)                              # the optimizer step that produced these parameter values (and the allocation point)
+        owner.params_ready(side, clear=False)              # ... also when that step runs on a stream of its own (the current stream still has to wait)
+        with torch.cuda.stream(side):
+            total_variation_add_grad(owner.grid.data, seed, wx, wy, wz, 'write')
+            ev = torch.cuda.Event()
+            ev.record(side)
+        self.seed = (seed, ev)
+
+    def take_seed(self, shape, device):
+        hit, self.seed = self.seed, None
+        if hit is None:
+            return None
+        seed, ev = hit
+        torch.cuda.current_stream(device).wait_event(ev)
+        if tuple(seed.shape) != tuple(shape) or seed.device != device:        # the grid was replaced in between (scale_volume_grid)
+            raise N.K4Error('total_variation_seed_grad: the grid changed shape between the seed and the backward pass')
+        return seed
+
+    def close(self):
+        """After the backward pass: a seed no lookup consumed becomes (or is added to) the gradient."""
+        if self.seed is not None:
+            g = self.owner.grid
+            seed = self.take_seed(g.shape, g.device)
+            g.grad = seed if g.grad is None else g.grad.add_(seed)
+
+    def backward(self, go, shape, pts, xyz_min, xyz_max):
+        """GridSample3D.backward: -> the dense gradient, or None with the sums left in the scratch image for MaskedAdam (k4_masked_adam_upd_sparse_cl[_seeded])."""
+        _, C_, X, Y, Z = shape
+        if self.early is not None or (self.route == 'sparse' and self.seed is None):
+            img = _scratch_image(go.device, C_, X, Y, Z, self)
+            if img is not None:
+                img.holder, n = self, pts.shape[0]
+                if n > 0:
+                    img.run(lambda: N.check(N.lib().k4_grid_sample_3d_backward_cl_scatter(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n,
+                                                                                           N.ptr(img.ws), N.stream()), 'grid_sample_3d_backward_cl_scatter'))
+                self.sums = True
+                return None
+            if self.early is not None:
+                raise N.K4Error('GridSample3D.backward: the scratch image of a grid whose step was split is gone')
+        gg = self.take_seed(shape, go.device)
+        if gg is None:
+            gg = torch.zeros(shape, dtype=torch.float32, device=go.device)
+        grid_sample_3d_backward(go, C_, X, Y, Z, pts, xyz_min, xyz_max, gg, self)
+        return gg
+
+    def image(self, cleared=False):
+        """(MaskedAdam) the scratch image its in-place step reads: this iteration's sums, or -- `cleared`, or a split step no backward reached -- all zero."""
+        g = self.owner.grid
+        img = _GSB_WS.get(g.device)
+        if self.sums and (img is None or img.holder is not self or img.shape != tuple(g.shape[1:])):
+            self.sums = False
+            img = None
+        elif not self.sums:
+            img = _scratch_image(g.device, *g.shape[1:], self)
+        elif cleared:
+            img.run(img.ws.zero_)
+        if img is None:
+            raise N.K4Error('the scratch image of the pending grid gradient is gone')
+        return img
+
+    def consumed(self):
+        """(MaskedAdam) the in-place step was launched: image and flags are all-zero behind it."""
+        img = _GSB_WS.get(self.owner.grid.device)
+        if img is not None and img.holder is self:
+            img.holder = None
+        self.sums, self.early, self.flagged = False, None, False
+
+    def sweep(self):
+        """Move the sums a scatter-only backward left in the scratch image into ``.grad`` (created when missing): the dense gradient after all."""
+        g = self.owner.grid
+        img = self.image()
+        if g.grad is None:
+            g.grad = torch.zeros_like(g, memory_format=torch.contiguous_format)
+        _, C_, X, Y, Z = g.shape
+        img.run(lambda: N.check(N.lib().k4_grid_sample_3d_backward_cl_sweep(C_, X, Y, Z, N.ptr(img.ws), N.f32(g.grad), N.stream()), 'grid_sample_3d_backward_cl_sweep'))
+        img.holder, self.sums = None, False
+
+    def abort(self):
+        """Back to idle.  After a finished iteration that only disarms.  After one the caller gave up on: the seed is forgotten (it holds a TV term of parameters a later
+        iteration no longer has), pending sums are dropped with their image, written flags with their buffer -- and a split step whose first part ran is COMPLETED from
+        the seed alone (its flagged voxels against a cleared image, the step count advanced): every voxel stepped once, a TV-only iteration for this grid."""
+        try:
+            if self.early is not None:
+                self.early[0].finish_split_step(self.owner, seed_only=True)
+        finally:
+            if self.sums:
+                img = _GSB_WS.get(self.owner.grid.device)
+                if img is not None and img.holder is self:
+                    img.drop()
+            if self.flagged:
+                self.flags = None
+            self.route = self.seed = self.early = None
+            self.sums = self.flagged = False
+
+
 def create_grid(type, **kwargs):
     if type == 'DenseGrid':
         return DenseGrid(**kwargs)
@@ -215,12 +348,10 @@ class DenseGrid(nn.Module):
         pts = xyz.reshape(-1, 3).contiguous()
         self.params_ready()
         if torch.is_grad_enabled() and self.grid.requires_grad:
-            sp = self._k4_split
-            if sp is not None and pts.shape[0] > 0:            # (a split optimizer step, JointTrainer.step: the voxels this lookup's backward will touch)
-                if sp.get('early', False):
-                    raise N.K4Error('DenseGrid.forward: a lookup under autograd after the first part of the split optimizer step')
+            flags = self.grad_route.lookup_flags() if pts.shape[0] > 0 else None
+            if flags is not None:                              # (a split optimizer step, JointTrainer.step: the voxels this lookup's backward will touch)
                 _, _, X, Y, Z = self.grid.shape
-                N.check(N.lib().k4_grid_flag_corners(X, Y, Z, N.f32(pts), N.f32(self.xyz_min), N.f32(self.xyz_max), pts.shape[0], N.ptr(sp['flags']), N.stream()),
+                N.check(N.lib().k4_grid_flag_corners(X, Y, Z, N.f32(pts), N.f32(self.xyz_min), N.f32(self.xyz_max), pts.shape[0], N.ptr(flags), N.stream()),
                         'k4_grid_flag_corners')
             out = GridSample3D.apply(self.grid, pts.detach(), self.xyz_min, self.xyz_max, self)
         else:
@@ -258,23 +389,14 @@ class DenseGrid(nn.Module):
         self.params_ready()
         total_variation_add_grad(self.grid, self.grid.grad, wx, wy, wz, dense_mode)
 
-    # ---- the dense TV term BEFORE the backward pass (no reference counterpart; joint_train.JointTrainer.step) ----
-    # The reference adds the term after backward (run_sr.py:1005-1011): zero-fill the gradient (4 B / voxel), scatter, then read grad + param
-    # and write grad (12 B) -- on the 339 M-float LLFF k0 that is 1.1 ms at the END of the iteration, where the next iteration's sample
-    # selection (a device-to-host read) waits for it.  Dense mode does not look at the gradient, so the term can be WRITTEN into a fresh
-    # buffer first (8 B / voxel, on a side stream under the iteration's host-paced phases) and the lookup's backward accumulates into
-    # that buffer instead of into zeros: grad = term + scatter, the same sum.
-    _k4_seed = None
-    # ---- iterations in which the lookups' backward is the ONLY contribution to the gradient and MaskedAdam skips zero-gradient voxels (the joint loop after
-    # tv_before: 290,000 of fern_lg_joint_l1's 300,000 iterations): the trainer sets _k4_sparse_grad, the backward then stops after its scatter (sums in the
-    # channel-last scratch image, `.grad` stays None, _k4_sparse_pending raised) and MaskedAdam.step updates exactly the touched voxels from there
-    # (k4_masked_adam_upd_sparse_cl) -- no 1.36 GB gradient cleared, swept into and read again per iteration.
-    _k4_sparse_grad = False
-    _k4_sparse_pending = False
-    # The step of this grid in two exact parts (MaskedAdam.early_step / _sparse_step; JointTrainer.step sets this for the iterations with a dense TV term written
-    # ahead): {'flags': uint8 [X*Y*Z], all-zero before the iteration's first lookup} -- lookups under autograd flag the voxels their backward will touch;
-    # early_step adds 'early', 'seed', 'step', 'hyper'
-    _k4_split = None
+    @property
+    def grad_route(self):
+        """The grid's GridGrad: where this iteration's gradient is and how it reaches the optimizer.  Created on first use; neither copied nor saved."""
+        r = self.__dict__.get('_k4_route')
+        if r is None:
+            r = self.__dict__['_k4_route'] = GridGrad(self)
+        return r
+
     # ---- an optimizer step of the grid running on a second stream (lib/masked_adam.MaskedAdam.update_on_side_stream) ----
     _k4_pending = None
 
@@ -310,7 +432,7 @@ class DenseGrid(nn.Module):
         memo[id(self)] = new
         import copy
         for k, v in self.__dict__.items():
-            if k in ('_k4_seed', '_k4_pending', '_k4_pending_seen', '_k4_sparse_grad', '_k4_sparse_pending', '_k4_split'):
+            if k in ('_k4_route', '_k4_pending', '_k4_pending_seen'):
                 continue
             new.__dict__[k] = copy.deepcopy(v, memo)
         return new
@@ -318,32 +440,14 @@ class DenseGrid(nn.Module):
     def total_variation_seed_grad(self, wx, wy, wz):
         """Start computing the dense TV term of the CURRENT parameter values into a new buffer (side stream).  The next backward pass
         through this grid accumulates into it; ``finish_grad_seed`` after the backward pass covers a pass that never reached the grid."""
-        cur = torch.cuda.current_stream(self.grid.device)
-        seed = torch.empty_like(self.grid.data, memory_format=torch.contiguous_format)
-        side = _tv_stream(self.grid.device)
-        side.wait_stream(cur)                              # the optimizer step that produced these parameter values (and the allocation point)
-        self.params_ready(side, clear=False)               # ... also when that step runs on a stream of its own (the current stream still has to wait)
-        with torch.cuda.stream(side):
-            total_variation_add_grad(self.grid.data, seed, wx, wy, wz, 'write')
-            ev = torch.cuda.Event()
-            ev.record(side)
-        self._k4_seed = (seed, ev)
+        self.grad_route.park_seed(wx, wy, wz)
 
     def _take_grad_seed(self, shape, device):
-        hit, self._k4_seed = self._k4_seed, None
-        if hit is None:
-            return None
-        seed, ev = hit
-        torch.cuda.current_stream(device).wait_event(ev)
-        if tuple(seed.shape) != tuple(shape) or seed.device != device:        # the grid was replaced in between (scale_volume_grid)
-            raise N.K4Error('total_variation_seed_grad: the grid changed shape between the seed and the backward pass')
-        return seed
+        return self.grad_route.take_seed(shape, device)
 
     def finish_grad_seed(self):
         """After the backward pass: a seed no lookup consumed becomes (or is added to) the gradient."""
-        if self._k4_seed is not None:
-            seed = self._take_grad_seed(self.grid.shape, self.grid.device)
-            self.grid.grad = seed if self.grid.grad is None else self.grid.grad.add_(seed)
+        self.grad_route.close()
 
     def get_dense_grid(self):
         self.params_ready()

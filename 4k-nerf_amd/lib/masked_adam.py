@@ -206,123 +206,108 @@ class MaskedAdam(torch.optim.Optimizer):
                                  'numel': [p.numel() for p in plist], 'ids': {id(p) for p in plist},
                                  'touched': [t for ts in items for t in (ts[0], ts[2], ts[3])]}
 
+    def _image_step(self, owner, name, launch, step, image=None, after=None, inputs=(), refuse=False):
+        """The ONE launch sequence of the steps that read a grid's gradient where the lookups' backward left it (early_step, finish_split_step, _sparse_step): lazy
+        state, tensor checks, the grid's side stream behind the current one (and `after`), ``launch(exp_avg, exp_avg_sq, step)`` -> return code, its completion handed
+        to the scratch `image` (the next scatter waits for it) and to the owner (every reader of the parameter waits for it), version bumps.  ``step`` maps the state's
+        count to the one the kernel uses; the caller stores it.  `refuse`: -> None instead of raising where the form does not apply, with nothing changed."""
+        param, state = owner.grid, self.state[owner.grid]
+        if not state:
+            state.update(step=0, exp_avg=torch.zeros_like(param, memory_format=torch.preserve_format),
+                         exp_avg_sq=torch.zeros_like(param, memory_format=torch.preserve_format))
+        tensors = (param, state['exp_avg'], state['exp_avg_sq'])
+        if any(not t.is_contiguous() or t.dtype != torch.float32 for t in tensors):
+            if refuse:
+                return None
+            raise ValueError(f'{name}: tensors must be contiguous fp32 device tensors')
+        n = step(int(state['step']))
+        cur, side = torch.cuda.current_stream(param.device), _side_stream(param.device)
+        side.wait_stream(cur)                                  # the scatter / the flags are complete, every read of the old values (lookups, the TV term's stencil) is issued
+        if after is not None:
+            side.wait_event(after)
+        for t in inputs:
+            t.record_stream(side)
+
+        def run():
+            with torch.cuda.stream(side):
+                return launch(*tensors[1:], n)
+        if image is not None:
+            ev = image.run(lambda: N.check(run(), name), side)
+        else:
+            rc = run()
+            if refuse and rc == N.K4_ERR_UNSUPPORTED:
+                return None
+            N.check(rc, name)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        owner.note_pending_update(ev)
+        for t in tensors:
+            torch.autograd.graph.increment_version(t)
+        return n
+
     @torch.no_grad()
     def early_step(self, owner, seed, seed_event):
         """First part of this iteration's step of ``owner.grid`` (a multi-channel grid whose step runs on the side stream), BEFORE the backward pass: every voxel the
-        lookups' backward cannot touch -- ``owner._k4_split['flags']`` marks those it can -- is stepped with gradient `seed` (the dense TV term written ahead, complete at
-        `seed_event`): for such a voxel that is the iteration's whole gradient.  The second part (the flagged voxels, gradient = seed + the scatter's sums) runs in
-        ``step`` through ``_sparse_step``.  Adam is elementwise: every element is stepped exactly once with its complete gradient, the same values as the one-pass step.
-        What it buys: the dense pass over the grid (1.8 ms for the LLFF k0) runs beside the rest of the iteration instead of between its backward pass and the next
-        iteration's lookup.  -> False (nothing done, take the one-pass path) when the split form does not apply."""
+        lookups' backward cannot touch -- the flags of the grid's gradient route (lib/grid.GridGrad, armed 'split') mark those it can -- is stepped with gradient `seed`
+        (the dense TV term written ahead, complete at `seed_event`): for such a voxel that is the iteration's whole gradient.  The second part (the flagged voxels,
+        gradient = seed + the scatter's sums) runs in ``step`` through ``finish_split_step``.  Adam is elementwise: every element is stepped exactly once with its complete
+        gradient, the same values as the one-pass step.  What it buys: the dense pass over the grid (1.8 ms for the LLFF k0) runs beside the rest of the iteration instead
+        of between its backward pass and the next iteration's lookup.  -> False (nothing done, take the one-pass path) when the split form does not apply."""
         from . import grid as G
-        param, sp = owner.grid, owner._k4_split
+        param, route = owner.grid, owner.grad_route
+        flags = route.split_flags()
         group = next((g for g in self.param_groups if any(p is param for p in g['params'])), None)
-        if sp is None or sp.get('early', False) or group is None or not group.get('skip_zero_grad') or not any(o is owner for o in self._side):
+        if flags is None or group is None or not group.get('skip_zero_grad') or not any(o is owner for o in self._side):
             return False
-        if not param.is_cuda or param.dim() != 5 or param.shape[1] <= 1 or param.grad is not None or not param.is_contiguous() or param.dtype != torch.float32:
+        if not param.is_cuda or param.dim() != 5 or param.shape[1] <= 1 or param.grad is not None:
             return False
         if self.per_lr is not None and self.per_lr.shape == param.shape:
             return False
         if seed.shape != param.shape or not seed.is_contiguous() or seed.dtype != torch.float32:
             return False
         _, C_, X, Y, Z = param.shape
-        if G._gsb_workspace(param.device, C_, X, Y, Z) is None:           # the second part reads the scatter's scratch image
+        if G._scratch_image(param.device, C_, X, Y, Z, route) is None:           # the second part reads the scatter's scratch image
             return False
-        (beta1, beta2), lr, eps = group['betas'], group['lr'], group['eps']
-        state = self.state[param]
-        if not state:
-            state.update(step=0, exp_avg=torch.zeros_like(param, memory_format=torch.preserve_format),
-                         exp_avg_sq=torch.zeros_like(param, memory_format=torch.preserve_format))
-        step = int(state['step']) + 1
-        for t in (state['exp_avg'], state['exp_avg_sq']):
-            if not t.is_contiguous() or t.dtype != torch.float32:
-                return False
-        cur, side = torch.cuda.current_stream(param.device), _side_stream(param.device)
-        side.wait_stream(cur)                                  # the flags are complete, every read of the old values (lookups, the TV term's stencil) is issued ...
-        side.wait_event(seed_event)                            # ... and the TV term itself is done
-        seed.record_stream(side)
-        sp['flags'].record_stream(side)
-        with torch.cuda.stream(side):
-            rc = N.lib().k4_masked_adam_upd_unflagged(N.ptr(param), N.ptr(seed), N.ptr(state['exp_avg']), N.ptr(state['exp_avg_sq']), C_, X * Y * Z, N.ptr(sp['flags']),
-                                                      step, float(beta1), float(beta2), float(lr), float(eps), int(_EARLY_WORKGROUPS), N.stream())
-            if rc == N.K4_ERR_UNSUPPORTED:
-                return False
-            N.check(rc, 'k4_masked_adam_upd_unflagged')
-            ev = torch.cuda.Event()
-            ev.record(side)
-        owner.note_pending_update(ev)
-        owner._k4_sparse_pending = True                        # the second part runs even if no backward pass reaches the grid (its flagged voxels: seed alone)
-        sp.update(early=True, seed=seed, step=step, hyper=(float(beta1), float(beta2), float(lr), float(eps)))
-        for t in (param, state['exp_avg'], state['exp_avg_sq']):
-            torch.autograd.graph.increment_version(t)
+        hyper = (float(group['betas'][0]), float(group['betas'][1]), float(group['lr']), float(group['eps']))
+        step = self._image_step(owner, 'k4_masked_adam_upd_unflagged', lambda m, v, n: N.lib().k4_masked_adam_upd_unflagged(
+            N.ptr(param), N.ptr(seed), N.ptr(m), N.ptr(v), C_, X * Y * Z, N.ptr(flags), n, *hyper, int(_EARLY_WORKGROUPS), N.stream()),
+            lambda n: n + 1, after=seed_event, inputs=(seed, flags), refuse=True)
+        if step is None:
+            return False
+        route.first_part_done(self, seed, step, hyper)                # (the state's step count advances with the second part: finish_split_step)
         return True
 
-    def _split_late_step(self, param, owner):
-        """Second part of a split step (early_step): the flagged voxels, gradient = seed + the sums the scatter left in the scratch image."""
-        from . import grid as G
-        sp = owner._k4_split
-        owner._k4_sparse_pending = False
-        owner._k4_split = None
-        _, C_, X, Y, Z = param.shape
-        hit = G._GSB_WS.get(param.device)
-        if hit is None or hit[0] != (C_, X, Y, Z):
-            raise N.K4Error('MaskedAdam: the scratch image of the pending grid gradient is gone')
+    @torch.no_grad()
+    def finish_split_step(self, owner, seed_only=False):
+        """Second part of a split step (early_step): the flagged voxels, gradient = seed + the sums the scatter left in the scratch image -- or, `seed_only` (the
+        iteration was given up after the first part, GridGrad.abort), the seed alone: a voxel no scatter reached is one this kernel handles anyway."""
+        param, route = owner.grid, owner.grad_route
+        flags, seed, step, hyper = route.split_part()
         state = self.state[param]
-        if int(state['step']) + 1 != sp['step'] or param.grad is not None:
+        if int(state['step']) + 1 != step or (param.grad is not None and not seed_only):
             raise N.K4Error('MaskedAdam: the second part of a split step does not follow its first part')
-        state['step'] = sp['step']
-        beta1, beta2, lr, eps = sp['hyper']
-        cur, side = torch.cuda.current_stream(param.device), _side_stream(param.device)
-        side.wait_stream(cur)                                  # the scatter is done
-        hit[1].record_stream(side)
-        with torch.cuda.stream(side):
-            N.check(N.lib().k4_masked_adam_upd_sparse_cl_seeded(N.ptr(param), N.ptr(state['exp_avg']), N.ptr(state['exp_avg_sq']), N.ptr(hit[1]), N.ptr(sp['seed']),
-                                                                N.ptr(sp['flags']), C_, X, Y, Z, int(sp['step']), beta1, beta2, lr, eps, N.stream()),
-                    'k4_masked_adam_upd_sparse_cl_seeded')
-            ev = torch.cuda.Event()
-            ev.record(side)
-        hit[2] = ev
-        owner.note_pending_update(ev)
-        for t in (param, state['exp_avg'], state['exp_avg_sq']):
-            torch.autograd.graph.increment_version(t)
+        _, C_, X, Y, Z = param.shape
+        img = route.image(cleared=seed_only)
+        state['step'] = self._image_step(owner, 'k4_masked_adam_upd_sparse_cl_seeded', lambda m, v, n: N.lib().k4_masked_adam_upd_sparse_cl_seeded(
+            N.ptr(param), N.ptr(m), N.ptr(v), N.ptr(img.ws), N.ptr(seed), N.ptr(flags), C_, X, Y, Z, n, *hyper, N.stream()), lambda n: step, image=img)
+        route.consumed()
 
     def _sparse_step(self, param, owner, masked, beta1, beta2, lr, eps):
-        """`param`'s gradient of this iteration is the sums its lookups' backward left in the channel-last scratch image (DenseGrid._k4_sparse_grad, set by the
+        """`param`'s gradient of this iteration is the sums its lookups' backward left in the channel-last scratch image (GridGrad route 'sparse', armed by the
         trainer for iterations without any other contribution to it): the masked update of exactly those voxels from there (k4_masked_adam_upd_sparse_cl), on
         the grid's side stream like the dense step.  Anything the in-place form does not cover (a `.grad` that exists after all, no zero-gradient skipping,
         a per-voxel learning rate on this tensor) sweeps the sums into the dense gradient instead and leaves the tensor to the regular path."""
-        from . import grid as G
-        if owner._k4_split is not None and owner._k4_split.get('early', False):
-            return self._split_late_step(param, owner)
+        route = owner.grad_route
+        if route.split_part() is not None:
+            return self.finish_split_step(owner)
         if param.grad is not None or not masked or (self.per_lr is not None and param.shape == self.per_lr.shape):
-            G.sweep_pending_grad(owner)
-            return
-        owner._k4_sparse_pending = False
+            return route.sweep()
         _, C_, X, Y, Z = param.shape
-        hit = G._GSB_WS.get(param.device)
-        if hit is None or hit[0] != (C_, X, Y, Z):
-            raise N.K4Error('MaskedAdam: the scratch image of the pending grid gradient is gone')
-        state = self.state[param]
-        if not state:
-            state.update(step=0, exp_avg=torch.zeros_like(param, memory_format=torch.preserve_format),
-                         exp_avg_sq=torch.zeros_like(param, memory_format=torch.preserve_format))
-        state['step'] += 1
-        for t in (param, state['exp_avg'], state['exp_avg_sq']):
-            if not t.is_contiguous() or t.dtype != torch.float32:
-                raise ValueError('k4_masked_adam_upd_sparse_cl: tensors must be contiguous fp32 device tensors')
-        cur, side = torch.cuda.current_stream(param.device), _side_stream(param.device)
-        side.wait_stream(cur)                                  # the scatter (and everything that read the old values) is done
-        hit[1].record_stream(side)
-        with torch.cuda.stream(side):
-            N.check(N.lib().k4_masked_adam_upd_sparse_cl(N.ptr(param), N.ptr(state['exp_avg']), N.ptr(state['exp_avg_sq']), N.ptr(hit[1]), C_, X, Y, Z,
-                                                         int(state['step']), float(beta1), float(beta2), float(lr), float(eps), N.stream()),
-                    'k4_masked_adam_upd_sparse_cl')
-            ev = torch.cuda.Event()
-            ev.record(side)
-        hit[2] = ev                                            # the next scatter into the image waits for the sweep half of this kernel
-        owner.note_pending_update(ev)
-        for t in (param, state['exp_avg'], state['exp_avg_sq']):
-            torch.autograd.graph.increment_version(t)
+        img = route.image()
+        self.state[param]['step'] = self._image_step(owner, 'k4_masked_adam_upd_sparse_cl', lambda m, v, n: N.lib().k4_masked_adam_upd_sparse_cl(
+            N.ptr(param), N.ptr(m), N.ptr(v), N.ptr(img.ws), C_, X, Y, Z, n, float(beta1), float(beta2), float(lr), float(eps), N.stream()),
+            lambda n: n + 1, image=img)
+        route.consumed()
 
     @torch.no_grad()
     def step(self):
@@ -330,7 +315,7 @@ class MaskedAdam(torch.optim.Optimizer):
             (beta1, beta2), lr, eps = group['betas'], group['lr'], group['eps']
             masked = group['skip_zero_grad']                   # KeyError without it, as upstream (masked_adam.py:45)
             for owner in self._side:
-                if owner._k4_sparse_pending and any(p is owner.grid for p in group['params']):
+                if owner.grad_route.pending and any(p is owner.grid for p in group['params']):
                     self._sparse_step(owner.grid, owner, masked, beta1, beta2, lr, eps)
             small = {}
             fast_ids = self._fast[id(group)]['ids'] if self._fast_step(group, masked, beta1, beta2, lr, eps) else ()

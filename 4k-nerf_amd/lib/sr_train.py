@@ -534,6 +534,11 @@ def forward_train(net, x, cond):
 # ---------------------------------------------------------------------------------------------------------------------
 # data parallelism: one bucketed all-reduce of the decoder's gradients
 # ---------------------------------------------------------------------------------------------------------------------
+def collectives_run(world):
+    """The data-path collectives of a job of `world` ranks are issued: always with several ranks, with one only in the RCCL smoke test (N.FORCE_COLLECTIVES)."""
+    return world > 1 or (N.FORCE_COLLECTIVES and dist.is_initialized())
+
+
 def allreduce_gradients(params, group=None, average=True):
     """Sum (and average) ``p.grad`` of `params` over the process group with ONE all-reduce of a flat fp32 bucket.
     Parameters without a gradient on this rank contribute zeros (every rank must pass the same parameter list).
@@ -550,7 +555,7 @@ def allreduce_gradients(params, group=None, average=True):
         pieces = [t.float() for t in pieces]
     flat = torch.cat(pieces)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
-    if world > 1 or (N.FORCE_COLLECTIVES and dist.is_initialized()):
+    if collectives_run(world):
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)          # backend "nccl" = RCCL on the GPUs, gloo in the CPU tests
         if average:
             flat /= world

@@ -72,12 +72,53 @@ def test_dense_grid_pending_update_hooks_are_inert_without_one():
     with torch.no_grad():
         g.grid.copy_(torch.randn_like(g.grid))
     g.params_ready()
-    assert g._k4_pending is None and g._k4_seed is None
+    assert g._k4_pending is None and g.grad_route.idle and not g.grad_route.pending            # no seed parked, nothing pending
     g2 = copy.deepcopy(g)
+    assert g2.grad_route is not g.grad_route and g2.grad_route.owner is g2                       # deepcopy does not carry the route object
     assert g2.grid is not g.grid and torch.equal(g2.grid, g.grid) and sorted(g2.state_dict()) == ['grid', 'xyz_max', 'xyz_min']
     g3 = copy.deepcopy(g).double()
     assert g3.grid.dtype == torch.float64 and torch.equal(g3.grid.float(), g.grid)
     assert torch.equal(g.get_dense_grid(), g.grid)
+
+
+def test_grid_gradient_route_transitions_that_launch_nothing():
+    """lib/grid.GridGrad (DenseGrid.grad_route): arming twice without finishing or aborting the iteration raises; abort() returns to idle from every state (and the
+    grid can be armed again); a split step's first part an optimizer refuses falls back to the one-pass route; a deepcopy of an armed grid is idle."""
+    import copy
+    import pytest
+    from nerf4k_amd import _native as N
+    from nerf4k_amd.lib import grid
+    g = grid.DenseGrid(3, [4, 5, 6], [0, 0, 0], [1, 1, 1])
+    r = g.grad_route
+    assert r is g.grad_route and r.idle and r.lookup_flags() is None
+    r.abort()
+    assert r.idle
+    with pytest.raises(ValueError):
+        r.arm('no such route')
+    assert r.idle
+    for route in ('dense', 'sparse', 'split'):
+        r.arm(route)
+        assert not r.idle and not r.pending
+        for again in ('dense', 'sparse', 'split'):
+            with pytest.raises(N.K4Error, match='still armed'):
+                r.arm(again)
+        flags = r.lookup_flags()
+        assert (flags is not None) == (route == 'split') and (r.split_flags() is flags)
+        if flags is not None:
+            assert flags.dtype == torch.uint8 and flags.numel() == 4 * 5 * 6 and int(flags.count_nonzero()) == 0
+        g2 = copy.deepcopy(g)
+        assert g2.grad_route.idle and g2.grad_route.lookup_flags() is None and sorted(g2.state_dict()) == ['grid', 'xyz_max', 'xyz_min']
+        r.abort()
+        assert r.idle and r.lookup_flags() is None and r.split_part() is None
+
+    class Refuses:
+        def early_step(self, owner, seed, event):
+            return False
+    r.arm('split')
+    r.first_part(Refuses())                                  # (no seed parked / an optimizer that refuses: the one-pass step after all)
+    assert not r.idle and r.lookup_flags() is None and r.split_flags() is None and r.split_part() is None
+    r.abort()
+    assert r.idle
 
 
 def test_fast_parameter_list_tracks_replaced_parameters():

@@ -236,7 +236,7 @@ def test_dense_tv_written_ahead_of_backward_and_side_stream_adam_equal_the_refer
         monkeypatch.setattr(joint_train, '_ADAM_SIDE', adam_side)                       # the k0 grid's optimizer step on a second stream
         tr = joint_train.JointTrainer(model, net, cfg, rk, n_train_images=17)
         hist = [float(tr.step(*batch, global_step=1 + i)['total']) for i in range(3)]
-        assert model.k0._k4_seed is None and model.density._k4_seed is None            # every seed was consumed (or folded in by finish_grad_seed)
+        assert model.k0.grad_route.idle and model.density.grad_route.idle              # every seed was consumed (or folded in by finish_grad_seed)
         assert (model.k0._k4_pending is not None) == adam_side                         # the last step's update may still be running ...
         sd = model.state_dict()                                                         # ... every reader waits for it: state_dict,
         if adam_side:                                                                   # (the event stays until the next update: a reader on ANOTHER stream waits too)
@@ -258,17 +258,17 @@ def test_dense_tv_written_ahead_of_backward_and_side_stream_adam_equal_the_refer
     z, model, net, rk, cfg, batch = _load_joint()
     g = model.k0
     g.total_variation_add_grad(0.3, 0.3, 0.1, 'seed')
-    assert g.grid.grad is None and g._k4_seed is not None
+    assert g.grid.grad is None and not g.grad_route.idle                            # (a seed is parked)
     g.finish_grad_seed()
     want = torch.zeros_like(g.grid)
     from nerf4k_amd.lib import grid as k4grid
     k4grid.total_variation_add_grad(g.grid, want, 0.3, 0.3, 0.1, True)
-    assert g._k4_seed is None and torch.equal(g.grid.grad, want)
+    assert g.grad_route.idle and torch.equal(g.grid.grad, want)
 
 
 def test_iterations_without_tv_update_k0_from_the_scatter_image(monkeypatch):
     """After tv_before (run_sr.py:1005-1011: no total variation; 290,000 of fern_lg_joint_l1's 300,000 iterations) JointTrainer.step leaves k0's gradient in
-    the scratch image of the lookups' backward and MaskedAdam updates the touched voxels from there (DenseGrid._k4_sparse_grad, MaskedAdam._sparse_step):
+    the scratch image of the lookups' backward and MaskedAdam updates the touched voxels from there (the 'sparse' route of DenseGrid.grad_route, MaskedAdam._sparse_step):
     four steps each way from the same state -- step 1 with dense TV (dense gradient both ways), steps 2-4 without -- same losses, parameters, moments and
     step counts (scatter atomics reorder sums: 1e-5 relative); `.grad` of k0 stays None in the in-place form; an iteration that raises drops its sums."""
     from nerf4k_amd.lib import masked_adam
@@ -286,13 +286,13 @@ def test_iterations_without_tv_update_k0_from_the_scatter_image(monkeypatch):
         for i in range(4):
             hist.append(float(tr.step(*batch, global_step=1 + i)['total']))
             assert (model.k0.grid.grad is None) == (sparse_on and i >= 1), i
-            assert not model.k0._k4_sparse_pending and not model.k0._k4_sparse_grad
+            assert model.k0.grad_route.idle and not model.k0.grad_route.pending
             assert model.density.grid.grad is not None
         st = tr.optimizer.state[model.k0.grid]
         assert st['step'] == 4
         sd = {k: v.detach().clone() for k, v in model.state_dict().items() if v.is_floating_point()}
         res.append((hist, sd, st['exp_avg'].clone(), st['exp_avg_sq'].clone()))
-        ws = k4grid._GSB_WS[model.k0.grid.device][1]
+        ws = k4grid._GSB_WS[model.k0.grid.device].ws
         assert int(ws.count_nonzero()) == 0                               # the image is all zero between iterations
     (h0, m0, a0, b0), (h1, m1, a1, b1) = res
     assert np.allclose(h1, h0, rtol=1e-6, atol=0), (h1, h0)
@@ -307,17 +307,20 @@ def test_iterations_without_tv_update_k0_from_the_scatter_image(monkeypatch):
         mp.setattr(joint_train, 'exchange_gradients', lambda *a, **k: (_ for _ in ()).throw(RuntimeError('skip this batch')))
         with pytest.raises(RuntimeError, match='skip this batch'):
             tr.step(*batch, global_step=9)
-    assert not model.k0._k4_sparse_pending and not model.k0._k4_sparse_grad and model.k0.grid.device not in k4grid._GSB_WS
+    assert model.k0.grad_route.idle and not model.k0.grad_route.pending and model.k0.grid.device not in k4grid._GSB_WS
     assert torch.equal(model.k0.grid.detach(), before)
     # ... and a pending gradient met by a step that cannot take the in-place form is swept into the dense tensor
-    model.k0._k4_sparse_grad = True
+    route = model.k0.grad_route
+    route.arm('sparse')
     with torch.enable_grad():
         rr, rgb_sr, ls = tr.forward(*batch, global_step=9)
         tr.optimizer.zero_grad(set_to_none=True)
         ls['total'].backward()
-    model.k0._k4_sparse_grad = False
-    k4grid.sweep_pending_grad(model.k0)
-    assert model.k0.grid.grad is not None and int(model.k0.grid.grad.count_nonzero()) > 0 and not model.k0._k4_sparse_pending
+    assert route.pending and model.k0.grid.grad is None
+    route.sweep()
+    assert model.k0.grid.grad is not None and int(model.k0.grid.grad.count_nonzero()) > 0 and not route.pending
+    route.abort()
+    assert route.idle
     assert torch.equal(model.k0.grid.detach(), before)
 
 
@@ -480,9 +483,9 @@ def test_split_grid_step_of_the_dense_tv_iterations_equals_the_one_pass_step(mon
         hist = []
         for i in range(3):
             hist.append(float(tr.step(*batch, global_step=1 + i)['total']))
-            assert model.k0._k4_split is None and model.k0._k4_seed is None and not model.k0._k4_sparse_pending
+            assert model.k0.grad_route.idle and not model.k0.grad_route.pending
             if split and i < 2:
-                assert model.k0.grid.grad is None and int(model.k0.__dict__['_k4_split_flags'].count_nonzero()) == 0
+                assert model.k0.grid.grad is None and int(model.k0.grad_route.flags.count_nonzero()) == 0
         monkeypatch.setattr(masked_adam.MaskedAdam, 'early_step', early)
         assert taken == ([True, True] if split else [])
         sd = model.state_dict()
@@ -498,3 +501,99 @@ def test_split_grid_step_of_the_dense_tv_iterations_equals_the_one_pass_step(mon
         _close(m1[k], m0[k].cpu(), k, rel=1e-5, abs_=1e-8)
     for a, b in zip(a1, a0):
         _close(a, b.cpu(), 'optimizer moment', rel=1e-5, abs_=1e-9)
+
+
+def _k0_sums_pending(tr, model, batch):
+    """Forward + backward of one patch with k0 on the 'sparse' route: its gradient stays in the scratch image."""
+    model.k0.grad_route.arm('sparse')
+    with torch.enable_grad():
+        rr, rgb_sr, ls = tr.forward(*batch, global_step=9)
+        tr.optimizer.zero_grad(set_to_none=True)
+        tr.optimizer_sr.zero_grad(set_to_none=True)
+        ls['total'].backward()
+    assert model.k0.grad_route.pending and model.k0.grid.grad is None
+
+
+def test_scratch_image_with_pending_sums_is_handed_to_its_holder_only(monkeypatch):
+    """While the scratch image holds a grid's pending gradient sums, a lookup backward for anybody else -- a grid of the same shape (it would sweep the foreign sums
+    into its own gradient) or of another shape (it would free them) -- raises K4Error, and the sums are intact: swept afterwards they are the dense gradient of a
+    run without the intruder (same non-zero voxels, values to the scatter atomics' 1e-5 relative)."""
+    from nerf4k_amd.lib import masked_adam, grid as k4grid
+    monkeypatch.setattr(masked_adam, '_MULTI_BELOW', 1000)
+    grads = []
+    for intruder in (False, True):
+        z, model, net, rk, cfg, batch = _load_joint()
+        tr = joint_train.JointTrainer(model, net, cfg, rk, n_train_images=17)
+        _k0_sums_pending(tr, model, batch)
+        if intruder:
+            _, C_, X, Y, Z = model.k0.grid.shape
+            dev = model.k0.grid.device
+            pts = model.k0.xyz_min + (model.k0.xyz_max - model.k0.xyz_min) * torch.rand([50, 3], device=dev)
+            for shape in ((C_, X, Y, Z), (C_, X + 1, Y, Z)):
+                gg = torch.zeros([1, *shape], device=dev)
+                with pytest.raises(N.K4Error, match='pending gradient'):
+                    k4grid.grid_sample_3d_backward(torch.ones([50, C_], device=dev), *shape, pts, model.k0.xyz_min, model.k0.xyz_max, gg)
+                assert int(gg.count_nonzero()) == 0
+                other = k4grid.DenseGrid(C_, list(shape[1:]), model.k0.xyz_min, model.k0.xyz_max).to(dev)
+                with torch.enable_grad(), pytest.raises(N.K4Error, match='pending gradient'):
+                    other(pts).sum().backward()
+            assert model.k0.grad_route.pending
+        model.k0.grad_route.sweep()
+        model.k0.grad_route.abort()
+        assert model.k0.grad_route.idle and int(k4grid._GSB_WS[model.k0.grid.device].ws.count_nonzero()) == 0
+        grads.append(model.k0.grid.grad.detach().clone())
+    assert int(grads[0].count_nonzero()) > 0 and torch.equal(grads[0] != 0, grads[1] != 0)
+    _close(grads[1], grads[0].cpu(), 'k0 gradient after the refused intruders', rel=1e-5, abs_=0)
+
+
+def test_iteration_given_up_after_the_first_part_of_a_split_step_is_completed_from_the_seed(monkeypatch):
+    """A dense-TV iteration whose k0 step was split (MaskedAdam.early_step) and that raises afterwards: GridGrad.abort completes the step from the seed alone, so k0,
+    its moments and its step count are EXACTLY those of a one-pass masked_adam_upd with the TV term as the whole gradient (Adam is elementwise; the two-part step
+    equals the one-pass step bit for bit, tests/test_optim_gpu.py); nothing of the iteration is left (route idle, flags and scratch image all zero or gone) and the
+    next iteration runs.  An iteration that raises BEFORE the first part leaves k0, its moments and its step count untouched."""
+    from nerf4k_amd.lib import masked_adam, grid as k4grid
+    monkeypatch.setattr(masked_adam, '_MULTI_BELOW', 1000)
+    z, model, net, rk, cfg, batch = _load_joint()
+    cfg = joint_train.JointCfg(dict(cfg, tv_before=100, tv_dense_before=100))
+    tr = joint_train.JointTrainer(model, net, cfg, rk, n_train_images=17)
+    tr.step(*batch, global_step=1)                                                  # (creates k0's optimizer state)
+    k0, route = model.k0.grid, model.k0.grad_route
+    st = tr.optimizer.state[k0]
+    pg = next(g for g in tr.optimizer.param_groups if any(p is k0 for p in g['params']))
+
+    def snapshot():
+        tr.optimizer.state_dict()                                                   # (waits for the grid's pending update)
+        torch.cuda.synchronize()
+        return [t.detach().clone() for t in (k0, st['exp_avg'], st['exp_avg_sq'])], int(st['step'])
+    # before the first part: the model's forward raises
+    before, step0 = snapshot()
+    with monkeypatch.context() as mp:
+        mp.setattr(type(model), 'forward', lambda *a, **k: (_ for _ in ()).throw(RuntimeError('no forward')))
+        with pytest.raises(RuntimeError, match='no forward'):
+            tr.step(*batch, global_step=2)
+    after, step1 = snapshot()
+    assert step1 == step0 and all(torch.equal(a, b) for a, b in zip(after, before)) and route.idle and not route.pending
+    # after it: the exchange raises.  Expected: the one-pass step of the pre-iteration tensors with the TV term alone
+    want = [t.clone() for t in before]
+    k0.grad = torch.empty_like(k0)
+    model.k0_total_variation_add_grad(cfg.weight_tv_k0 / 17, 'write')
+    tv, k0.grad = k0.grad, None
+    masked_adam.masked_adam_upd(*want[:1], tv, *want[1:], step0 + 1, *pg['betas'], pg['lr'], pg['eps'])
+    taken = []
+    early = masked_adam.MaskedAdam.early_step
+    with monkeypatch.context() as mp:
+        mp.setattr(masked_adam.MaskedAdam, 'early_step', lambda self, *a: taken.append(early(self, *a)) or taken[-1])
+        mp.setattr(joint_train, 'exchange_gradients', lambda *a, **k: (_ for _ in ()).throw(RuntimeError('skip this batch')))
+        with pytest.raises(RuntimeError, match='skip this batch'):
+            tr.step(*batch, global_step=2)
+    assert taken == [True]
+    got, step2 = snapshot()
+    assert step2 == step0 + 1 and route.idle and not route.pending
+    for a, b, name in zip(got, want, ('k0', 'exp_avg', 'exp_avg_sq')):
+        assert torch.equal(a, b), (name, float((a - b).abs().max()))
+    img = k4grid._GSB_WS.get(k0.device)
+    assert img is None or (img.holder is None and int(img.ws.count_nonzero()) == 0)
+    assert route.flags is None or int(route.flags.count_nonzero()) == 0
+    # ... and the next iteration is a normal one
+    assert np.isfinite(float(tr.step(*batch, global_step=3)['total']))
+    assert snapshot()[1] == step0 + 2 and route.idle
