@@ -10,7 +10,9 @@ configs/llff/fern_lg_joint_l1.py) on this package's HIP training graph:
 
 The adversarial term of the "+gan" recipes (run_sr.py:678-690, 916-957, 1016-1049) runs when a discriminator is handed in (``net_d``,
 lib/sr_unetdisc.UNetDiscriminatorSN): its generator loss joins ``total``, and after the two optimizer steps the discriminator takes its own
-step on the real patch and the detached decoder output.  The perceptual / style terms (weight_pcp, weight_style; VGG19) raise.
+step on the real patch and the detached decoder output.  The perceptual / style terms (weight_pcp, weight_style; run_sr.py:670-678, 934-945) run when
+a loss module is handed in (``cri_perceptual``, lib/sr_loss.PerceptualLoss with the VGG19 weights loaded by the caller): they join ``total`` after the
+high-resolution L1 term and in front of the adversarial one.  The network is frozen, so nothing of it is exchanged between data-parallel ranks.
 
 Data parallelism (one 64x64 patch per rank, run_sr.py:829-835): the decoder's 15.8 MB of gradients, the rgbnet and every other
 small tensor travel in ONE flat all-reduce (lib/sr_train.allreduce_gradients); the voxel grids do not -- `k0.grid` is 1.36 GB
@@ -135,8 +137,8 @@ class JointCfg(dict):
     @classmethod
     def fern_lg_joint_l1_gan(cls, **over):
         """configs/llff/fern_lg_joint_l1+gan.py: fern_lg_joint_l1 with weight_pcp=0.5, weight_gan=0.05, weight_style=0.2.  The preset carries the
-        perceptual / style weights as the configuration file states them; JointTrainer raises on them (VGG19 is not part of this package), so a
-        caller who wants the adversarial term alone passes ``weight_pcp=0, weight_style=0``."""
+        perceptual / style weights as the configuration file states them; JointTrainer needs ``cri_perceptual`` for them (the caller loads the VGG19
+        weights: lib/sr_loss.PerceptualLoss), so a caller who wants the adversarial term alone passes ``weight_pcp=0, weight_style=0``."""
         cfg = dict(weight_pcp=0.5, weight_gan=0.05, weight_style=0.2)
         cfg.update(over)
         return cls.fern_lg_joint_l1(**cfg)
@@ -146,9 +148,19 @@ class JointTrainer:
     """Optimizers + one-iteration method of the joint loop.  ``render_kwargs`` as run_sr.py:690-702 builds them
     (``render_depth=True``; ``rand_bkgd`` for LLFF); ``n_train_images`` = len(rays_o_tr), the TV weights' divisor (:1008-1011)."""
 
-    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, near_clip=None, net_d=None):
-        if cfg_train.weight_pcp > 0 or cfg_train.get('weight_style', 0) > 0:
-            raise NotImplementedError('perceptual / style losses (run_sr.py:934-945; basicsr PerceptualLoss on VGG19) are not provided')
+    def __init__(self, model, net_sr, cfg_train, render_kwargs, n_train_images, sr_ratio=4, num_cond=1, dim_rend=3, group=None, near_clip=None, net_d=None,
+                 cri_perceptual=None):
+        weight_style = cfg_train.get('weight_style', 0)
+        if (cfg_train.weight_pcp > 0 or weight_style > 0) and cri_perceptual is None:
+            raise NotImplementedError('weight_pcp / weight_style > 0 need the loss module: JointTrainer(..., cri_perceptual=sr_loss.PerceptualLoss(layer_weights, '
+                                      'perceptual_weight=weight_pcp, style_weight=weight_style)) with the VGG19 weights loaded by the caller '
+                                      '(load_vgg_state_dict; run_sr.py:670-678)')
+        if weight_style > 0 and not cfg_train.weight_pcp > 0:
+            raise NotImplementedError('weight_style > 0 with weight_pcp == 0: run_sr.py:934 evaluates both terms under `weight_pcp > 0` only and would drop the '
+                                      'style term silently; set weight_style=0 or weight_pcp > 0')
+        if cfg_train.weight_pcp > 0 and (cri_perceptual.perceptual_weight != cfg_train.weight_pcp or cri_perceptual.style_weight != weight_style):
+            raise ValueError(f'cri_perceptual carries perceptual_weight={cri_perceptual.perceptual_weight}, style_weight={cri_perceptual.style_weight}; the '
+                             f'configuration states weight_pcp={cfg_train.weight_pcp}, weight_style={weight_style} (run_sr.py:678)')
         if cfg_train.weight_gan > 0 and net_d is None:
             raise NotImplementedError('weight_gan > 0 needs a discriminator: JointTrainer(..., net_d=sr_unetdisc.UNetDiscriminatorSN(3, 64)) (run_sr.py:679-690)')
         if num_cond != 1 or dim_rend != 3:
@@ -165,6 +177,8 @@ class JointTrainer:
         self._after_march = None
         # the adversarial term (run_sr.py:679-690); with weight_gan == 0 a discriminator handed in is ignored: the step is the one without it
         self.net_d = net_d if cfg_train.weight_gan > 0 else None
+        # the perceptual / style terms (run_sr.py:670-678); with weight_pcp == 0 a module handed in is ignored
+        self.cri_perceptual = cri_perceptual if cfg_train.weight_pcp > 0 else None
         self.optimizer_d = self.cri_gan = None
         if self.net_d is not None:
             self.cri_gan = sr_unetdisc.GANLoss(gan_type='vanilla', loss_weight=cfg_train.weight_gan)
@@ -259,6 +273,14 @@ class JointTrainer:
         cond = rr['depth'].reshape(1, pr, pc, 1).movedim(-1, 1)                          # num_cond == 1 (run_sr.py:894-897)
         rgb_sr = self._decoder(rgb_cache, cond)                                          # run_sr.py:918
         ls = self.losses(rr, rgb_sr, target, target_4x, pr, pc, len(rays_o))
+        if self.cri_perceptual is not None:                      # run_sr.py:934-937: after the L1 terms, in front of the adversarial one
+            s = self.sr_ratio
+            rgb_hr = target_4x.detach().reshape(s * pr, s * pc, 3).movedim(-1, 0).unsqueeze(0)
+            ls['pcp'], style = self.cri_perceptual(rgb_sr, rgb_hr)
+            ls['total'] = ls['total'] + ls['pcp']
+            if style is not None:
+                ls['style'] = style
+                ls['total'] = ls['total'] + style
         if self.net_d is not None:                               # generator phase (run_sr.py:920-922, 946-957): D frozen, one more summand of `total`
             for p in self.net_d.parameters():
                 p.requires_grad = False

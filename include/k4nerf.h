@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      17      /* 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      18      /* 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -818,6 +818,45 @@ int k4_sn_project_grad(const float* g, const float* weight_orig, const float* u,
  *   loss[0] = scale * mean(softplus(target_is_real ? -x : x));   grad_logits = grad_loss[0] (NULL: 1) * scale / n * d softplus.  One launch each. */
 int k4_gan_loss_fwd(const float* logits, int64_t n, int32_t target_is_real, float scale, float* loss, void* stream);
 int k4_gan_loss_bwd(const float* logits, int64_t n, int32_t target_is_real, float scale, const float* grad_loss, float* grad_logits, void* stream);
+
+/* ---- the perceptual / style terms of the "+gan" joint recipes (csrc/k4_vgg.hip; run_sr.py:670-678, 934-945: basicsr PerceptualLoss on VGG19, whose formulas
+ * lib/sr_loss.py:123-188 restates: L1 of features :158-172, Gram matrix :175-188) ------------------------------------------------------------------------
+ * All activations NHWC fp32, `batch` images back to back (the decoder output and the ground-truth patch travel as a batch of two).  Arithmetic of the matrix
+ * products: the exact 3-term bf16 splits of k4_disc_conv_s2, the five correction products in an accumulator of their own (fp32-equivalent).  Every entry point is recordable on a launch tape; none uses float atomics.
+ *
+ * k4_vgg_conv3x3, by `mode` (ksize 3: pad 1; ksize 1: a per-pixel product):
+ *   K4_VGG_CONV_FWD    v = bias + sum x[p - 1 + d][ci] W[co][ci][d];  y_pre (NULL: not kept) = v, the tap of a `convK_J` layer;  y (NULL: not kept) = relu ? max(v, 0) : v;
+ *                      y_pool (NULL: none; H, W even, relu set) = the 2x2 stride-2 max pool of y.  w_split = k4_vgg_pack_weight(..., K4_VGG_CONV_FWD)
+ *   K4_VGG_CONV_DGRAD  x = dY with cin = the layer's outputs, y = dX with cout = the layer's inputs: v = sum dY[p + 1 - d][co] W[co][ci][d];
+ *                      y = (mask == NULL || mask[.] > 0 ? v : 0) + (add == NULL ? 0 : add[.]): the ReLU backward of the layer that produced this layer's input, from its
+ *                      saved activation (torch's rule: act > 0), and a loss seed added on the way.  w_split = k4_vgg_pack_weight(..., K4_VGG_CONV_DGRAD)
+ *   cin % 16 == 0, x 16-byte aligned (K4_ERR_UNSUPPORTED otherwise).  Operand: k4_vgg_weight_bytes(outputs, inputs, ksize) =
+ *   [inputs/16][3 terms][ksize^2][2][32*ceil(outputs/32)][8] bf16, written by k4_vgg_pack_weight from w [cout][cin][ksize][ksize] once per weight load.
+ * k4_vgg_conv1_1 / _bwd: the first layer on planar images x0, x1 (x1 may be NULL) [3][H][W] with (x - mean) / std in the load (zero padding of the normalised
+ *   image); y, y_pre [n][H][W][cout], cout % 16 == 0.  _bwd: grad_x [3][H][W] planar = (1 / std) * the input gradient of grad_y [H][W][cout] (one image).
+ * k4_vgg_pool_bwd: grad_full [H][W][C] = (the FIRST maximum of its 2x2 window of `act` in (dy, dx) order (aten max_pool2d) && (!relu_mask || act > 0) ? grad_pooled : 0) + add.
+ * k4_vgg_l1_fwd: loss[0] (fp64: the caller sums the layers' terms before the one fp32 rounding) = scale * mean|a - b| (fp64 partial sums in a fixed order; workspace k4_vgg_l1_workspace_bytes(n));  _bwd: grad_a = grad_loss[0] (NULL: 1) *
+ *   scale / n * sign(a - b) + add (NULL: 0).
+ * k4_vgg_gram: gram [2][C][C] = f f^T / (C * n_pix) of the two images f [2][n_pix][C] (lib/sr_loss.py:175-188); C % 64 == 0; the pixel bands' partial sums go to
+ *   `workspace` (k4_vgg_gram_workspace_bytes) and are added in band order.  k4_vgg_gram_bwd_pack: the one-tap operand M (k4_vgg_weight_bytes(C, C, 1)) with which
+ *   k4_vgg_conv3x3(f_x, ksize 1, K4_VGG_CONV_DGRAD) gives d(scale * mean|G_x - G_g|) / d f_x = (2 / (C n_pix)) S_sym f_x, S = grad_loss * scale / C^2 * sign(G_x - G_g). */
+#define K4_VGG_CONV_FWD   0
+#define K4_VGG_CONV_DGRAD 1
+int64_t k4_vgg_weight_bytes(int32_t outputs, int32_t inputs, int32_t ksize);
+int k4_vgg_pack_weight(const float* w, int32_t cout, int32_t cin, int32_t ksize, int32_t form, void* w_split, void* stream);
+int k4_vgg_conv3x3(const float* x, int32_t cin, int32_t H, int32_t W, int32_t batch, const void* w_split, int32_t ksize, const float* bias,
+                   float* y, float* y_pre, float* y_pool, int32_t cout, int32_t mode, int32_t relu, const float* mask, const float* add, void* stream);
+int k4_vgg_conv1_1(const float* x0, const float* x1, int32_t H, int32_t W, const float* mean, const float* stdv, const float* w, const float* bias,
+                   int32_t cout, float* y, float* y_pre, void* stream);
+int k4_vgg_conv1_1_bwd(const float* grad_y, int32_t H, int32_t W, int32_t cout, const float* w, const float* stdv, float* grad_x, void* stream);
+int k4_vgg_pool_bwd(const float* act, const float* grad_pooled, const float* add, int32_t H, int32_t W, int32_t channels, int32_t relu_mask,
+                    float* grad_full, void* stream);
+int64_t k4_vgg_l1_workspace_bytes(int64_t n);
+int k4_vgg_l1_fwd(const float* a, const float* b, int64_t n, float scale, void* workspace, double* loss, void* stream);
+int k4_vgg_l1_bwd(const float* a, const float* b, int64_t n, float scale, const float* grad_loss, const float* add, float* grad_a, void* stream);
+int64_t k4_vgg_gram_workspace_bytes(int32_t n_pix, int32_t channels);
+int k4_vgg_gram(const float* f, int32_t n_pix, int32_t channels, float* workspace, int64_t workspace_bytes, float* gram, void* stream);
+int k4_vgg_gram_bwd_pack(const float* gram, int32_t n_pix, int32_t channels, float scale, const float* grad_loss, void* w_split, void* stream);
 
 #ifdef __cplusplus
 }
