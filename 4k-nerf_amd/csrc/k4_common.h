@@ -52,8 +52,13 @@ __device__ __forceinline__ float2 k4_ld2(const float* p) {
     return make_float2(v.x, v.y);
 }
 
-// C round(): halves away from zero (the reference's maskcache_lookup, render_utils_kernel.cu:385-387)
-__device__ __forceinline__ int k4_round_half_away(float x) { return (int)roundf(x); }
+// C round(): halves away from zero (the reference's maskcache_lookup, render_utils_kernel.cu:385-387), as an integer.
+// (int)roundf(x) is 7 vector instructions (trunc, fraction, compare, select, copysign, add, convert); adding the largest fp32 below 0.5 with
+// x's sign and truncating is 3 and gives the same integer for EVERY fp32 x: below 2^23 the sum's rounding never crosses an integer that
+// round() would not cross (0.5 itself would: 0.49999997 + 0.5 must stay below 1), from 2^23 on x is an integer and the sum rounds back to
+// it; NaN and +-inf pass through both forms.  Checked over all 2^32 bit patterns
+// (tests/test_round_identity.py covers the boundary cases, profiles/geom_fast_path.md records the exhaustive run).
+__device__ __forceinline__ int k4_round_half_away(float x) { return (int)(x + copysignf(0.49999997f, x)); }
 
 // bijective XCD-aware block remap (hardware places block b on XCD b%8; give each XCD a contiguous
 // range of logical workgroups so neighbours share that XCD's L2).  Speed only, never correctness.
@@ -146,6 +151,7 @@ struct K4Env {
     int debug;           // K4_DEBUG        (0) ablation bits of the marcher kernels, profiling only
     int sr_debug;        // K4_SR_DEBUG     (0) profiling bits of the decoder kernels (1: input channel stride 0 = no memory traffic, WRONG results; 2..16: phases of the 3x3 kernel off; 32: SFT layers on the unpipelined kernel; exact ones: 2048: row kernel instead of the K-split 3x3 kernel on small images, 4096: per-tap weight-gradient kernel instead of the nine-tap one)
     bool no_fast_shade;  // K4_DEBUG & 1024: the shading kernel's general path on shapes the FAST path covers (A/B, tests: identical outputs)
+    bool no_fast_geom;   // K4_DEBUG & 16384: the geometry kernel's general path on shapes its FAST path covers (A/B, tests: identical outputs)
 };
 // Settled by measurement and no longer switchable (the evidence is in profiles/ and DESIGN.md): geometry kernel bounded for 5 waves per
 // SIMD (6 spilled), serpentine ray order inside an 8x8 tile, one row of workgroup tiles per XCD band, persistent shading grid of 2 workgroups

@@ -170,6 +170,7 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 #define K4_TKTAB 256              // MPI: k/(Ns-1) for k < K4_TKTAB is tabulated once per workgroup (an IEEE division costs ~10 VALU per sample)
 #define K4_ELIST 512              // kept (ray, group) entries enumerated at a time (ray sub-batches when 64 rays x groups exceed it)
 #define K4_GRP 16                 // samples per skip group
+#define K4_GEOM_DEBUG_BITS (16 | 32 | 128 | 4096 | 8192)      // the K4_DEBUG ablation bits the geometry kernel reads (general instantiation only)
 struct Geom2Lds {
     float raytab[64][8];     // [0..2] start xyz, [3] bits(kq0) | [4..6] dir xyz, [7] bits(kq1): the bundle's rays and THIS wave's depth range [kq0,kq1) of each
     unsigned qk[K4_RING];    // ring of mask-passing samples: ray_local<<24 | step (residual < 64 + one group of 256)
@@ -198,8 +199,15 @@ __device__ __forceinline__ float tk_of(const MarchParams& P, const float* tktab,
 #else
 #define K4_GSTAMP(SLOT) do { } while (0)
 #endif
-template <int MODE, bool COUNT, int MINW>
+// FAST: the reference's LLFF configuration (configs/llff/llff_default_lg.py: mpi_depth 256, stepsize 1.0) fixed at compile time, like the shading
+// kernel's FAST -- MPI render instantiation, interval == 1 and thres > 0 (one raw2alpha form, both filters on), ONE launch (no slab arithmetic),
+// occupancy summary present, n_samples <= K4_TKTAB (=> at most 4 groups per ray and depth quarter: never `big`, one ray batch; every k a lane can
+// form, the padding lanes of a last group included, is below roundup16(n_samples) <= K4_TKTAB: step positions come from the table without the
+// division fallback and its branch), Z >= 2, no ablation bit.  It only drops code these conditions make dead: every expression tree is the general
+// path's -> the same bits (tests/test_geom_fast_gpu.py).  The host predicate is in launch_march; K4_DEBUG & 16384 forces the general path.
+template <int MODE, bool COUNT, int MINW, bool FAST = false>
 __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P) {
+    static_assert(!FAST || (MODE == MODE_MPI && !COUNT), "FAST is the MPI render instantiation");
 #ifdef K4_GEOM_TIMING
     unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, glast = __builtin_amdgcn_s_memtime();
 #endif
@@ -216,8 +224,10 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
         for (int i = (int)threadIdx.x; i < K4_TKTAB; i += 256) tktab[i] = (float)i / P.nsm1;
     }
     __syncthreads();
-    const bool unit_interval = P.interval == 1.f;
-    const bool use_thres = P.thres > 0.f;
+    const bool unit_interval = FAST || P.interval == 1.f;
+    const bool use_thres = FAST || P.thres > 0.f;
+    const int dbg = FAST ? 0 : P.debug;                                // ablation bits (general path only)
+    auto tk_at = [&](int k) -> float { if constexpr (FAST) return tktab[k]; else return tk_of<MODE>(P, tktab, k); };
     unsigned long long n_inb = 0, n_mask = 0, n_alpha = 0, n_shade = 0, n_behind = 0;
 
     // static, XCD-banded bundle map, one bundle per workgroup: per-XCD or global work queues measured 6-25 % slower -- the
@@ -232,7 +242,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     uint2* const ent_base = P.entries + (size_t)B.id * (size_t)P.ent_stride;
     // the four runs of records of this launch (one per wave, depth-ascending): quarters of the bundle's slice, or -- split form -- runs of
     // span0 (first launch) / span1 (second launch) samples per ray laid out one behind the other: 4 (span0 + span1) <= max_steps rounded up
-    const int slab = (MODE == MODE_MPI && !COUNT) ? P.slab : 0;
+    const int slab = (MODE == MODE_MPI && !COUNT && !FAST) ? P.slab : 0;
     const int span0 = P.split_k >> 2, span1 = (((P.n_samples - P.split_k) + 63) >> 6) << 4;      // samples per ray and wave of the two launches
     const int quarter = slab == 0 ? (P.ent_stride >> 2) : (slab == 1 ? span0 : span1) * 64;
     const int run0 = slab == 2 ? 4 * span0 * 64 : 0;                              // records in front of this launch's first run
@@ -266,17 +276,21 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
         L.acnt[lane] = 0;
     }
     K4_GSTAMP(0);                                                                // workgroup prologue + ray setup
-    if (P.debug & 4096) ngrp = 0;                                                // ablation (WRONG results): prologue, arrival and the empty scan only -- the kernel's fixed cost
-    if (P.debug & 8192) { if (lane == 0 && wv == 0) P.counts[B.id] = 0; break; } // ablation: not even the arrival / scan
+    if (dbg & 4096) ngrp = 0;                                                // ablation (WRONG results): prologue, arrival and the empty scan only -- the kernel's fixed cost
+    if (dbg & 8192) { if (lane == 0 && wv == 0) P.counts[B.id] = 0; break; } // ablation: not even the arrival / scan
     int gq = ngrp;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) gq = max(gq, __shfl_xor(gq, off));
     gq = __builtin_amdgcn_readfirstlane(gq);
-    const bool big = gq > 64;                                                    // more groups than mask bits: enumerate every group (g < 1024: host check)
+    // FAST: MPI rays take nsteps == n_samples <= K4_TKTAB samples (host predicate), so a depth quarter is one 64-sample block: at most 4 groups,
+    // and every k formed below is < roundup16(n_samples) <= K4_TKTAB -- the table reads tktab[k] rest on both
+    static_assert(K4_TKTAB <= 256 && K4_TKTAB % K4_GRP == 0, "FAST: one 64-sample block per depth quarter, k < K4_TKTAB");
+    if (FAST) __builtin_assume(gq <= K4_TKTAB / (4 * K4_GRP));
+    const bool big = !FAST && gq > 64;                                                    // more groups than mask bits: enumerate every group (g < 1024: host check)
 
     // ---- stage P: which 16-sample groups of my ray can touch an occupied voxel? ----
     unsigned long long keep = ngrp >= 64 ? ~0ull : ((1ull << ngrp) - 1ull);
-    if (!COUNT && P.occ != nullptr && !big) {
+    if (!COUNT && (FAST || P.occ != nullptr) && !big) {
         keep = 0ull;
         const float4 ra = *reinterpret_cast<const float4*>(&L.raytab[lane][0]);
         const float4 rb = *reinterpret_cast<const float4*>(&L.raytab[lane][4]);
@@ -286,7 +300,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
 #pragma unroll 4
         for (int j = 0; j < gq; ++j) {                                            // (unrolled: the summary fetches of 4 groups fly together)
             const int ka = kq0 + K4_GRP * j, kb = min(ka + K4_GRP - 1, kq1 - 1);
-            const float ta = tk_of<MODE>(P, tktab, j < ngrp ? ka : 0), tb = tk_of<MODE>(P, tktab, j < ngrp ? kb : 0);
+            const float ta = tk_at(j < ngrp ? ka : 0), tb = tk_at(j < ngrp ? kb : 0);
             // the two end samples, with the arithmetic of stage A (same fmaf chain, same round())
             const int iax = k4_round_half_away(fmaf(fmaf(rb.x, ta, ra.x), P.msx, P.mtx)), ibx = k4_round_half_away(fmaf(fmaf(rb.x, tb, ra.x), P.msx, P.mtx));
             const int iay = k4_round_half_away(fmaf(fmaf(rb.y, ta, ra.y), P.msy, P.mty)), iby = k4_round_half_away(fmaf(fmaf(rb.y, tb, ra.y), P.msy, P.mty));
@@ -331,7 +345,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
             const int rl = (int)(key >> 24);
             const int k = (int)(key & 0xffffffu);
             const float* rt = L.raytab[rl];
-            const float tk = tk_of<MODE>(P, tktab, k);
+            const float tk = tk_at(k);
             const float px = fmaf(rt[4], tk, rt[0]), py = fmaf(rt[5], tk, rt[1]), pz = fmaf(rt[6], tk, rt[2]);
             const float nx = k4_norm_coord_r(px, P.minx, P.lenx, P.rlenx);
             const float ny = k4_norm_coord_r(py, P.miny, P.leny, P.rleny);
@@ -347,11 +361,11 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
             const unsigned r00 = (unsigned)(x0 * P.Y + y0) * (unsigned)P.Z, r01 = (unsigned)(x0 * P.Y + y1) * (unsigned)P.Z;
             const unsigned r10 = (unsigned)(x1 * P.Y + y0) * (unsigned)P.Z, r11 = (unsigned)(x1 * P.Y + y1) * (unsigned)P.Z;
             pkey[s2] = key; pfx[s2] = ux; pfy[s2] = uy; pfz[s2] = uz;
-            if (P.debug & 16) {                                           // ablation: no density fetch
+            if (dbg & 16) {                                           // ablation: no density fetch
                 const float c = __uint_as_float(0x3f000000u + (r00 & 0xffffu));
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) pdl[s2][c4] = pdh[s2][c4] = c;
-            } else if (P.Z >= 2) {
+            } else if (FAST || P.Z >= 2) {
                 const float2 v0 = k4_ld2(P.density + r00 + zb), v1 = k4_ld2(P.density + r01 + zb);
                 const float2 v2 = k4_ld2(P.density + r10 + zb), v3 = k4_ld2(P.density + r11 + zb);
                 pdl[s2][0] = v0.x; pdh[s2][0] = v0.y; pdl[s2][1] = v1.x; pdh[s2][1] = v1.y;
@@ -423,7 +437,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     // batch of 64 rays for the LLFF configuration: 4 groups per ray and quarter).
     const int q16 = lane >> 4, l15 = lane & 15;
     int rb = 64;
-    while (rb > 1 && rb * gq > K4_ELIST) rb >>= 1;
+    if (!FAST) while (rb > 1 && rb * gq > K4_ELIST) rb >>= 1;
     for (int r0 = 0; r0 < 64; r0 += rb) {
         int total;
         {
@@ -445,9 +459,10 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
             }
         }
         K4_GSTAMP(2);                                                            // entry list
-        // groups of 4 items: the 4 occupancy bytes are fetched together (one memory round trip per 256 samples), branch-free
-        // (clamped index, validity folded into the predicate); all 4 are consumed (ballots) before any density batch is
-        // issued, so the only fetches in flight across the next group's wait are that batch's
+        // groups of 4 items: the 4 occupancy bytes are fetched together (one memory round trip per 256 samples); the index is clamped and
+        // validity folded into the predicate, but the code is not branch-free: the compiler puts exec-mask branches around the byte fetch
+        // (and, in the general instantiation, around the bbox test and the division fallback of tk_of; FAST has no fallback).  All 4 are
+        // consumed (ballots) before any density batch is issued, so the only fetches in flight across the next group's wait are that batch's
         for (int e0 = 0; e0 < total; e0 += 16) {
             unsigned mbyte[4];
             bool inbv[4];
@@ -461,7 +476,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
                 const float4 ra = *reinterpret_cast<const float4*>(&L.raytab[r_][0]);
                 const float4 rbv = *reinterpret_cast<const float4*>(&L.raytab[r_][4]);
                 const int k = __float_as_int(ra.w) + g_ * K4_GRP + l15;
-                const float tk = tk_of<MODE>(P, tktab, k);
+                const float tk = tk_at(k);
                 const float px = fmaf(rbv.x, tk, ra.x), py = fmaf(rbv.y, tk, ra.y), pz = fmaf(rbv.z, tk, ra.z);
                 const bool inb = ev && (k < __float_as_int(rbv.w)) &&
                     !((P.minx > px) | (P.miny > py) | (P.minz > pz) | (P.maxx < px) | (P.maxy < py) | (P.maxz < pz));
@@ -525,7 +540,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) maxc = max(maxc, __shfl_xor(maxc, off));
         maxc = __builtin_amdgcn_readfirstlane(maxc);
-        if (P.debug & 32) maxc = 0;                                    // ablation: no transmittance scan
+        if (dbg & 32) maxc = 0;                                    // ablation: no transmittance scan
         // (the NEXT four alphas are requested before the current four are folded into T: the loop is a load -> dependent chain -> store
         //  sequence per iteration, 25 % of the kernel's wave time in round 5's form)
         float an[4];
@@ -564,7 +579,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
         const uint2* const run = ent_base + run0 + (size_t)w * quarter;
         int naw = na_sh[w];
         na_all += naw;
-        if (P.debug & 128) naw = 0;                                    // ablation: no survivor compaction (nothing shaded)
+        if (dbg & 128) naw = 0;                                    // ablation: no survivor compaction (nothing shaded)
         for (int base = 0; base < naw; base += 64) {
             const int i = base + lane;
             const bool v = i < naw;
@@ -1043,7 +1058,12 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
     const int n_cu = k4_num_cus();
     {
         // one workgroup (4 waves = 4 depth quarters) per bundle
-        // MINW = waves per SIMD the register allocation is bounded for: 5 (85 VGPRs, no spills); 6 (80 VGPRs, 6 spilled) measured slower
+        // MINW = waves per SIMD the register allocation is bounded for: 5 (general path: 96 VGPRs, 4 spilled; FAST: 85, none); 6 (80 VGPRs) spills
+        // in both forms (general: 17 registers, measured 3 % slower in round 3; FAST: 4, measured 1 % slower, profiles/geom_fast_path.md)
+        // FAST: the LLFF configuration (see k4_geom3_kernel); anything else -- DVGO, the counting instantiation, a split scene, stepsize != 1,
+        // a scene without the occupancy summary, more than K4_TKTAB samples, any ablation bit the kernel reads -- takes the general instantiation
+        const bool gfast = MODE == MODE_MPI && !P.counters && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr &&
+                           P.Z >= 2 && P.n_samples <= K4_TKTAB && (P.debug & K4_GEOM_DEBUG_BITS) == 0 && !k4_env().no_fast_geom;
 #ifdef K4_GEOM_TIMING
         if (P.counters) { MarchParams Q = P; Q.timing = P.counters + 8; Q.counters = nullptr;
                           hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q); } else
@@ -1057,6 +1077,7 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
             Q.slab = 2;
             hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q);
         }
+        else if (gfast) hipLaunchKernelGGL((k4_geom3_kernel<MODE_MPI, false, 5, true>), dim3((unsigned)nwg * 4), block, 0, st, P);
         else hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, P);
     }
     int rc = k4_check_launch();
@@ -1191,7 +1212,8 @@ extern "C" int k4_abi_version(void) { return K4_ABI_VERSION; }
 
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static const K4Env g_k4_env = {        // namespace-scope constant: initialised while the library is loaded, immutable afterwards
-    env_int("K4_GEOM_SKIP", 1), env_int("K4_DEBUG", 0), env_int("K4_SR_DEBUG", 0), (env_int("K4_DEBUG", 0) & 1024) != 0};
+    env_int("K4_GEOM_SKIP", 1), env_int("K4_DEBUG", 0), env_int("K4_SR_DEBUG", 0), (env_int("K4_DEBUG", 0) & 1024) != 0,
+    (env_int("K4_DEBUG", 0) & 16384) != 0};
 const K4Env& k4_env() { return g_k4_env; }
 int k4_num_cus() {
     static int n_cu[K4_MAX_DEVICES];

@@ -157,6 +157,11 @@ int k4_mlp_b2_layer1_terms(void);    /* NT1 of the default section: 2 (3 in A/B 
  *                  shaded samples, alpha-pass samples BEHIND their ray's T<1e-3 stop (density evaluated, then dropped by the
  *                  transmittance scan: what a depth-ordered geometry stage could skip), 0, 0, 0}, ACCUMULATED
  *                  (caller zeroes) -- the counts SURVEY 8(d)'s algorithmic-bytes formula needs.
+ * Both kernels have a FAST instantiation for the LLFF configuration (shape fixed at compile time, same expression trees, same bits as
+ * their general paths).  K4_DEBUG bits (environment, read once at load) that keep exact results: 1024 = general shading path,
+ * 2048 = one geometry launch whatever grid->depth_split says, 16384 = general geometry path (k4_march_mpi_fwd with interval == 1,
+ * fast_color_thres > 0, depth_split == 0, an occupancy summary, n_samples <= 256 and no counters takes the FAST one otherwise).
+ * Every other bit is a profiling ablation with WRONG results.
  * ------------------------------------------------------------------------------------------- */
 int64_t k4_march_workspace_bytes(int64_t n_rays, int32_t img_w, int32_t max_steps);
 

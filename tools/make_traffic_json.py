@@ -11,7 +11,8 @@ for line in open(md):
     if m:
         full = m.group(1).strip()
         cur = full.split('<')[0]
-        if cur == 'k4_geom3_kernel' and 'true' in full:          # the sample-counting instantiation (bench's counter frames): not the product launch
+        # the sample-counting instantiation (bench's counter frames; COUNT is the second template argument -- the last one is FAST): not the product launch
+        if cur == 'k4_geom3_kernel' and re.match(r'k4_geom3_kernel<\s*\d+,\s*true', full):
             cur = None
         continue
     m = re.match(r'\| (FETCH_SIZE|WRITE_SIZE) \| ([0-9.e+]+) \|', line)
