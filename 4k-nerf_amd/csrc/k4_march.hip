@@ -17,17 +17,19 @@
 //     the contiguous axis of the [X][Y][Z] grids, so the occupancy byte and the density gathers of a wave coalesce into a
 //     few 128-B lines that the neighbouring ray re-uses from L1/L2.  Mask-passing samples are compacted across rays
 //     before the density stage (all lanes busy); transmittance is the reference's exact sequential product, run
-//     transposed (lane = ray) by wave 0 after a workgroup barrier.  Survivors (w > thres) are compacted straight into the
-//     bundle's slice of a workspace as 8-byte {ray,step | weight} records -- ~9 per ray instead of the reference's
-//     256 x 60 B of per-sample intermediates.
+//     transposed (lane = ray) by whichever wave of the workgroup finishes its quarter last (an LDS arrival counter, no barrier).
+//     Survivors (w > thres) go to the front of the bundle's slice of a workspace as 8-byte {ray,step | weight} records -- ~9
+//     per ray instead of the reference's 256 x 60 B of per-sample intermediates: appended by the scan itself in the FAST
+//     (LLFF) instantiation, compacted in place by a second pass over the records in the general one.
 // K2  k4_shade_kernel  (VALU / gather bound)
 //     persistent waves pull bundles from a queue; 64 records at a time, lane = sample: 8-corner k0 gather from the
 //     channel-last repack, features to LDS, then the rgbnet MLP on the matrix cores as C^T[neuron][sample] = W . X --
 //     by default with exact 3-term bf16 splits on v_mfma_f32_32x32x16_bf16 (fp32-equivalent), optionally with
 //     v_mfma_f32_32x32x2_f32 (exact fp32 FMA chains).  Weights are pre-arranged in operand order and LDS resident; the C
 //     layout of layer n IS the B-operand layout of layer n+1 (K is walked in accumulator-register order), so activations
-//     never leave registers and there is no cross-lane traffic between layers.  A segmented wave scan folds w*rgb / w*s
-//     into per-ray LDS accumulators; 5 floats per ray are the only other global writes.
+//     never leave registers and there is no cross-lane traffic between layers.  w*rgb / w*s are added in fixed point to
+//     per-ray LDS accumulators (integer ds_add_u64: exact, so a bundle's records may come in any order); 5 floats per ray
+//     are the only other global writes.
 // Superseded variants (a per-ray K1 with every stage on the same lanes, a K1 with global / per-XCD work queues, a K2 with
 // LDS-DMA prefetch of the next batch's gathers at one workgroup per CU) were measured and dropped: DESIGN.md 5, profiles/.
 // Deterministic: no global atomics on the data path, fixed summation order.
@@ -54,7 +56,8 @@ struct MarchParams {
     const float* mlp; int mlp_floats; int mlp_floats_b3; int mlp_floats_b2; int dim0; int k1p; int vpe; int spe; int k0_skip;
     int n_samples;          // MPI: samples per ray
     int max_steps;          // capacity per ray in the workspace
-    int ent_stride;         // records per bundle in the workspace: 64 * max_steps rounded up to 256 (4 depth quarters)
+    int ent_stride;         // records per bundle in the workspace: FIVE quarters (ent_stride_of)
+    int quarter;            // records per quarter: 16 * max_steps rounded up to 256 = the capacity of one wave's run of alpha-passing records
     int depth_n;            // denominator of s = (k+0.5)/depth_n
     float nsm1;             // MPI: (float)(n_samples-1)
     float stepdist, near_, far_, shift, interval, thres, bg;
@@ -156,6 +159,9 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 //      next group's occupancy round trip); alpha-passing samples are appended to the bundle's workspace slice as {ray,step|alpha};
 //   C. transposed transmittance scan, lane = RAY: the reference's exact sequential product, writing w over alpha;
 //   D. in-place compaction of the w > thres survivors -> the records the shading kernel consumes.
+//   FAST instantiation: C and D are ONE pass -- the scan appends a survivor to the front of the slice the moment it has its weight
+//   (no write-back of w, no second read of the records; a stopped ray reads nothing more).  The raw runs therefore start one quarter
+//   into the slice; the shading kernel does not care about the order of a bundle's records.
 // -----------------------------------------------------------------------------------------------------
 #ifndef K4_GEOM_MIN_WG
 #define K4_GEOM_MIN_WG 1
@@ -165,6 +171,9 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 #endif
 #ifndef K4_SHADE_SCAN
 #define K4_SHADE_SCAN 0           // 1: per-ray sums by a segmented wave scan + one LDS atomic per run (the earlier form)
+#endif
+#ifndef K4_GEOM_LDS_PAD
+#define K4_GEOM_LDS_PAD 0            // A/B builds only: see the kernel
 #endif
 #define K4_RING 512
 #define K4_TKTAB 256              // MPI: k/(Ns-1) for k < K4_TKTAB is tabulated once per workgroup (an IEEE division costs ~10 VALU per sample)
@@ -186,8 +195,8 @@ __device__ __forceinline__ float tk_of(const MarchParams& P, const float* tktab,
 
 // The 4 waves of a workgroup share ONE bundle of 64 rays, wave w taking depth quarter w of every ray (a wave's footprint between
 // two neighbouring rays is 4 rows x 256 B: the row reuse of adjacent rays hits L1/L2).  Records of quarter w go to quarter w of
-// the bundle's workspace slice; after a workgroup barrier wave 0 runs the transmittance scan over the four runs of each ray in
-// depth order and compacts the survivors.  (Since v4 there is no barrier: the last wave to finish its quarter does this.)
+// the bundle's workspace slice (FAST: quarter w + 1, the first quarter takes the survivors); the last wave to finish its quarter
+// runs the transmittance scan over the four runs of each ray in depth order and compacts the survivors (no barrier).
 // COUNT: the sample counters of bench.py / the tests (k4_march_*_fwd `counters`) are a separate instantiation that visits EVERY
 // sample (no skipping), so that the counters are the algorithm's sample counts and the render path carries no
 // counting code.
@@ -218,6 +227,12 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     const int lane = k4_lane();
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     Geom2Lds& L = lds_all[wv];
+#if K4_GEOM_LDS_PAD > 0
+    // A/B builds only (tools/build_variant.sh): extra LDS bytes per workgroup, to hold the resident workgroups per CU at a chosen number
+    // (22.5 KB: 7 per CU; padded to 32 KB: 5) while everything else stays the same -- profiles/geom_tail_append.md
+    __shared__ int lds_pad[K4_GEOM_LDS_PAD / 4];
+    if (P.n_rays < 0) reinterpret_cast<volatile int*>(lds_pad)[threadIdx.x] = 0;
+#endif
     if (blockIdx.x == 0 && threadIdx.x == 0) *P.qhead = 0;            // work queue of the shading kernel that follows
     if (threadIdx.x == 0) arrived = 0;
     if (MODE == MODE_MPI) {
@@ -244,9 +259,10 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     // span0 (first launch) / span1 (second launch) samples per ray laid out one behind the other: 4 (span0 + span1) <= max_steps rounded up
     const int slab = (MODE == MODE_MPI && !COUNT && !FAST) ? P.slab : 0;
     const int span0 = P.split_k >> 2, span1 = (((P.n_samples - P.split_k) + 63) >> 6) << 4;      // samples per ray and wave of the two launches
-    const int quarter = slab == 0 ? (P.ent_stride >> 2) : (slab == 1 ? span0 : span1) * 64;
+    const int quarter = slab == 0 ? P.quarter : (slab == 1 ? span0 : span1) * 64;
     const int run0 = slab == 2 ? 4 * span0 * 64 : 0;                              // records in front of this launch's first run
-    uint2* const ent = ent_base + run0 + (size_t)wv * quarter;                   // this wave's run of records
+    // FAST: the raw runs start ONE quarter into the slice, [0, quarter) is where the scan appends the survivors (see the tail)
+    uint2* const ent = ent_base + run0 + (size_t)(FAST ? wv + 1 : wv) * quarter;  // this wave's run of records
 
     // ---- ray setup, lane = ray of the bundle ----
     const int myray = ray_index(P, B, lane);
@@ -519,76 +535,149 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     prev = __builtin_amdgcn_readfirstlane(prev);
     if (prev != 3) break;                                              // not the last: done
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    // ---- stage C: transposed transmittance scan, lane = ray (render_utils_kernel.cu:591-603); a ray's records are
-    // 4 runs (one per depth quarter), visited in depth order ----
     float T = 1.f;
     bool stopped = false;
-    if (slab == 2) { T = myray >= 0 ? P.out_ainv[myray] : 1.f; stopped = T < 1e-3f; }      // where the first launch's scan left this ray
-    const bool any_rec = (na_sh[0] | na_sh[1] | na_sh[2] | na_sh[3]) != 0;                  // (wave-uniform) a bundle without records: nothing to scan or compact
+    float my_ainv;                                                     // alphainv_last of ray `lane` (1 if it has no samples)
+    int cnt = 0, na_all = 0;                                           // (wave-uniform) survivors written / alpha-passing records of the bundle
+    if constexpr (FAST) {
+        // ---- stages C + D in one pass: transposed transmittance scan, lane = ray (render_utils_kernel.cu:591-603), that appends each
+        // w > thres survivor to the front of the slice as soon as its weight exists.  Per quarter w in depth order and per rank j of a
+        // ray's records in it: one 8-byte load of the raw {key, alpha} (the next four ranks are requested before the current four are
+        // folded into T), the reference's sequential product, a ballot over the 64 rays and one coalesced 8-byte store per surviving
+        // lane.  No weight goes back to the raw run and nothing is read twice; a ray that has stopped loads nothing more, and the pass
+        // ends when no ray has both records left and transmittance left.  Record order of a bundle: quarter, rank within the ray, ray
+        // slot (the general path: quarter, ray, depth) -- the shading kernel's per-ray sums are exact integer adds and a sample's MLP
+        // column does not depend on its lane or batch, so the pixels are the same bits (tests/test_geom_tail_gpu.py).
+        // No hazard between the appends and the raw records still to be read:
+        //   - a wave's run holds na_v <= quarter records (FAST: one 64-sample block per ray and quarter, 64 rays), and survivors are a
+        //     subset of the records already read: while quarter w is scanned every append lands below sum_{v<=w} na_v <= (w + 1) * quarter;
+        //   - every raw record not yet read lies at or above (w + 1) * quarter, where run w starts;
+        //   - the largest index ever written is (w + 1) * quarter - 1, reached only when every sample of every ray survives.
+        // So the two regions never meet and the pointers below do not alias.
+        uint2* __restrict__ const surv = ent_base;
+        const bool any_rec = (na_sh[0] | na_sh[1] | na_sh[2] | na_sh[3]) != 0;              // (wave-uniform) a bundle without records: nothing to scan
 #pragma unroll
-    for (int w = 0; w < 4 && any_rec; ++w) {
-        uint2* const run = ent_base + run0 + (size_t)w * quarter;
-        const int c = lds_all[w].acnt[lane];
-        int incl = c;
+        for (int w = 0; w < 4 && any_rec; ++w) {
+            if (__ballot(!stopped) == 0ull) break;                     // every ray has stopped: the remaining quarters are behind the stop
+            const uint2* __restrict__ const run = ent_base + (size_t)(w + 1) * quarter;
+            const int c = lds_all[w].acnt[lane];
+            int incl = c;
 #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
-        const int seg = incl - c;
-        int maxc = c;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) maxc = max(maxc, __shfl_xor(maxc, off));
-        maxc = __builtin_amdgcn_readfirstlane(maxc);
-        if (dbg & 32) maxc = 0;                                    // ablation: no transmittance scan
-        // (the NEXT four alphas are requested before the current four are folded into T: the loop is a load -> dependent chain -> store
-        //  sequence per iteration, 25 % of the kernel's wave time in round 5's form)
-        float an[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) an[u] = (u < c && maxc > 0) ? __uint_as_float(run[seg + u].y) : 0.f;
-        for (int j0 = 0; j0 < maxc; j0 += 4) {
-            float a[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = an[u];
-            if (j0 + 4 < maxc) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) an[u] = (j0 + 4 + u < c) ? __uint_as_float(run[seg + j0 + 4 + u].y) : 0.f;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int v = __shfl_up(incl, off);
+                if (lane >= off) incl += v;
             }
+            const uint2* __restrict__ const mine = run + (incl - c);   // this ray's records of the quarter, depth-ascending
+            // Software pipeline, one step = four ranks: [wait for this step's records] [store the PREVIOUS step's survivors] [request the
+            // next step's records] [fold this step into T].  Loads and stores sit in exec-mask branches, so the compiler cannot count
+            // them: any wait it places behind them is vmcnt(0).  In this order the only wait of a step comes first, when nothing
+            // younger than the records it needs is in flight -- the next step's loads and this step's stores fly under the arithmetic.
+            uint2 en[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (COUNT) n_behind += __popcll(__ballot(j0 + u < c && stopped));      // density was evaluated for a sample the scan then drops
-                if (j0 + u < c) {
-                    float wgt = -1.f;                                  // behind the early stop: never shaded
-                    if (!stopped) {
-                        wgt = T * a[u];
-                        T = fmaf(-T, a[u], T);                         // == (float)((double)T*(1.-a)): the CUDA source's fp64 product, one rounding
+            for (int u = 0; u < 4; ++u) en[u] = (u < c && !stopped) ? mine[u] : make_uint2(0u, 0u);
+            uint2 pe[4];                                               // survivors of the previous step: {key, weight} ...
+            int ppos[4];                                               // ... and where they go
+            bool pshade[4] = {false, false, false, false};
+            for (int j0 = 0; ; j0 += 4) {
+                const bool more = __ballot(j0 < c && !stopped) != 0ull;    // (wave-uniform) some ray has records left and transmittance left
+                uint2 e[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { e[u] = en[u]; asm volatile("" : "+v"(e[u].x), "+v"(e[u].y)); }      // the step's one vmcnt wait lands here
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) if (pshade[u]) surv[ppos[u]] = pe[u];
+                if (!more) break;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) en[u] = (j0 + 4 + u < c && !stopped) ? mine[j0 + 4 + u] : make_uint2(0u, 0u);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    float wgt = 0.f;
+                    const bool act = j0 + u < c && !stopped;
+                    if (act) {
+                        const float a = __uint_as_float(e[u].y);
+                        wgt = T * a;
+                        T = fmaf(-T, a, T);                            // == (float)((double)T*(1.-a)): the CUDA source's fp64 product, one rounding
                         if (T < 1e-3f) stopped = true;                 // the crossing sample is still counted (:597-600)
                     }
-                    run[seg + j0 + u].y = __float_as_uint(wgt);
+                    const bool shade = act && wgt > P.thres;
+                    const uint64_t sm = __ballot(shade);
+                    pshade[u] = shade; ppos[u] = cnt + (int)k4_prefix(sm); pe[u] = make_uint2(e[u].x, __float_as_uint(wgt));
+                    cnt += __popcll(sm);
                 }
             }
         }
-    }
-    const float my_ainv = T;                                           // alphainv_last of ray `lane` (1 if it has no samples)
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // ---- stage D: keep w > thres, compacted to the front of the bundle's slice, run order preserved ----
-    int cnt = slab == 2 ? __builtin_amdgcn_readfirstlane(P.counts[B.id]) : 0, na_all = 0;      // second launch: append behind the first launch's survivors
+        my_ainv = T;
+    } else {
+        // ---- stage C: transposed transmittance scan, lane = ray (render_utils_kernel.cu:591-603); a ray's records are
+        // 4 runs (one per depth quarter), visited in depth order ----
+        if (slab == 2) { T = myray >= 0 ? P.out_ainv[myray] : 1.f; stopped = T < 1e-3f; }      // where the first launch's scan left this ray
+        const bool any_rec = (na_sh[0] | na_sh[1] | na_sh[2] | na_sh[3]) != 0;                  // (wave-uniform) a bundle without records: nothing to scan or compact
 #pragma unroll
-    for (int w = 0; w < 4 && any_rec; ++w) {
-        const uint2* const run = ent_base + run0 + (size_t)w * quarter;
-        int naw = na_sh[w];
-        na_all += naw;
-        if (dbg & 128) naw = 0;                                    // ablation: no survivor compaction (nothing shaded)
-        for (int base = 0; base < naw; base += 64) {
-            const int i = base + lane;
-            const bool v = i < naw;
-            const uint2 e = run[v ? i : 0];
-            const float wgt = __uint_as_float(e.y);
-            const bool shade = v && (use_thres ? (wgt > P.thres) : (wgt >= 0.f));
-            const uint64_t sm = __ballot(shade);
-            if (shade) ent_base[cnt + k4_prefix(sm)] = e;               // cnt + prefix <= position of e: never overtakes the reads
-            cnt += __popcll(sm);
+        for (int w = 0; w < 4 && any_rec; ++w) {
+            uint2* const run = ent_base + run0 + (size_t)w * quarter;
+            const int c = lds_all[w].acnt[lane];
+            int incl = c;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int v = __shfl_up(incl, off);
+                if (lane >= off) incl += v;
+            }
+            const int seg = incl - c;
+            int maxc = c;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) maxc = max(maxc, __shfl_xor(maxc, off));
+            maxc = __builtin_amdgcn_readfirstlane(maxc);
+            if (dbg & 32) maxc = 0;                                    // ablation: no transmittance scan
+            // (the NEXT four alphas are requested before the current four are folded into T: the loop is a load -> dependent chain -> store
+            //  sequence per iteration, 25 % of the kernel's wave time in round 5's form)
+            float an[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) an[u] = (u < c && maxc > 0) ? __uint_as_float(run[seg + u].y) : 0.f;
+            for (int j0 = 0; j0 < maxc; j0 += 4) {
+                float a[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a[u] = an[u];
+                if (j0 + 4 < maxc) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) an[u] = (j0 + 4 + u < c) ? __uint_as_float(run[seg + j0 + 4 + u].y) : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (COUNT) n_behind += __popcll(__ballot(j0 + u < c && stopped));      // density was evaluated for a sample the scan then drops
+                    if (j0 + u < c) {
+                        float wgt = -1.f;                                  // behind the early stop: never shaded
+                        if (!stopped) {
+                            wgt = T * a[u];
+                            T = fmaf(-T, a[u], T);                         // == (float)((double)T*(1.-a)): the CUDA source's fp64 product, one rounding
+                            if (T < 1e-3f) stopped = true;                 // the crossing sample is still counted (:597-600)
+                        }
+                        run[seg + j0 + u].y = __float_as_uint(wgt);
+                    }
+                }
+            }
+        }
+        my_ainv = T;                                           // alphainv_last of ray `lane` (1 if it has no samples)
+
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // ---- stage D: keep w > thres, compacted to the front of the bundle's slice, run order preserved ----
+        cnt = slab == 2 ? __builtin_amdgcn_readfirstlane(P.counts[B.id]) : 0;      // second launch: append behind the first launch's survivors
+#pragma unroll
+        for (int w = 0; w < 4 && any_rec; ++w) {
+            const uint2* const run = ent_base + run0 + (size_t)w * quarter;
+            int naw = na_sh[w];
+            na_all += naw;
+            if (dbg & 128) naw = 0;                                    // ablation: no survivor compaction (nothing shaded)
+            for (int base = 0; base < naw; base += 64) {
+                const int i = base + lane;
+                const bool v = i < naw;
+                const uint2 e = run[v ? i : 0];
+                const float wgt = __uint_as_float(e.y);
+                const bool shade = v && (use_thres ? (wgt > P.thres) : (wgt >= 0.f));
+                const uint64_t sm = __ballot(shade);
+                if (shade) ent_base[cnt + k4_prefix(sm)] = e;               // cnt + prefix <= position of e: never overtakes the reads
+                cnt += __popcll(sm);
+            }
         }
     }
     if (lane == 0) P.counts[B.id] = cnt;
@@ -1058,8 +1147,9 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
     const int n_cu = k4_num_cus();
     {
         // one workgroup (4 waves = 4 depth quarters) per bundle
-        // MINW = waves per SIMD the register allocation is bounded for: 5 (general path: 96 VGPRs, 4 spilled; FAST: 85, none); 6 (80 VGPRs) spills
-        // in both forms (general: 17 registers, measured 3 % slower in round 3; FAST: 4, measured 1 % slower, profiles/geom_fast_path.md)
+        // MINW = waves per SIMD the register allocation is bounded for: 5 (general path: 96 VGPRs, 4 spilled; 6 = 80 VGPRs spills 17 registers, measured
+        // 3 % slower in round 3).  FAST takes 72 VGPRs without a spill since its tail is one pass (85 before: profiles/geom_fast_path.md), so its
+        // residency is set by the 22 KB of LDS -- 7 workgroups per CU -- and no longer by the bound (profiles/geom_tail_append.md)
         // FAST: the LLFF configuration (see k4_geom3_kernel); anything else -- DVGO, the counting instantiation, a split scene, stepsize != 1,
         // a scene without the occupancy summary, more than K4_TKTAB samples, any ablation bit the kernel reads -- takes the general instantiation
         const bool gfast = MODE == MODE_MPI && !P.counters && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr &&
@@ -1123,8 +1213,12 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
     return k4_check_launch();
 }
 
-// records per bundle: 64 rays x max_steps rounded up to a whole number of 64-sample blocks per depth quarter
-static inline int64_t ent_stride_of(int32_t max_steps) { return 64 * (((int64_t)max_steps + 255) / 256 * 256); }
+// records per quarter of a bundle's slice: a wave's 64 rays x its depth quarter of max_steps rounded up to a whole number of 64-sample blocks
+static inline int64_t ent_quarter_of(int32_t max_steps) { return 16 * (((int64_t)max_steps + 255) / 256 * 256); }
+// records per bundle: FIVE quarters.  General instantiation: the four waves' runs of alpha-passing records in quarters 0..3, survivors
+// compacted in place to the front, quarter 4 unused.  FAST instantiation: survivors appended from the front of quarter 0 while the
+// runs are read from quarters 1..4 (see the kernel's tail).  Either way the shading kernel reads records [0, counts[b]) of the slice.
+static inline int64_t ent_stride_of(int32_t max_steps) { return 5 * ent_quarter_of(max_steps); }
 
 // workspace: [records nb x ent_stride x 8 B][counts nb] | [queue head .. queue length: 64 ints] | [jobs: nb x 8 B], each 256-aligned
 struct WsLayout { int64_t counts, qhead, jobs, total; };
@@ -1179,6 +1273,7 @@ static int fill_common(MarchParams& P, const float* rays_o, const float* rays_d,
     P.max_steps = max_steps;
     if (ent_stride_of(max_steps) > 0x7fffffff) return K4_ERR_BAD_ARG;
     P.ent_stride = (int)ent_stride_of(max_steps);
+    P.quarter = (int)ent_quarter_of(max_steps);
     const int64_t nb = (int64_t)n_workgroups(n_rays, img_w) * 4;
     const WsLayout L = ws_layout(nb, ent_stride_of(max_steps));
     P.entries = (uint2*)workspace;

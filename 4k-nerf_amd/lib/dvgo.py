@@ -538,6 +538,9 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
             rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
             depth = torch.empty([Nr], dtype=torch.float32, device=dev)
             ainv = torch.empty([Nr], dtype=torch.float32, device=dev)
+        if k4_counters is not None:             # the counting launch adds to counters[0..4] unconditionally (include/k4nerf.h: uint64[8])
+            assert (torch.is_tensor(k4_counters) and k4_counters.is_cuda and k4_counters.dtype == torch.int64 and k4_counters.is_contiguous()
+                    and k4_counters.numel() >= 8), 'k4_counters: a contiguous CUDA int64 tensor of at least 8 elements'
         use_live = bool(k4_live_mask and k4_counters is None)
 
         def build():

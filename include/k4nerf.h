@@ -152,6 +152,12 @@ int k4_mlp_b2_layer1_terms(void);    /* NT1 of the default section: 2 (3 in A/B 
  *   workspace : device scratch of >= k4_march_workspace_bytes(n_rays, img_w, max_steps) bytes (the compacted
  *             {ray,step,weight} records between the two kernels; worst-case sized, sparsely touched);
  *             max_steps = n_samples for MPI.  Owned by the caller, reusable across calls on one stream.
+ *             Per bundle of 64 rays: FIVE quarters of 16 x max_steps (rounded up to 256) 8-byte records -- four runs of
+ *             alpha-passing records, one per depth quarter, and the survivors in front of them (the FAST geometry
+ *             instantiation appends survivors to the first quarter while it reads the runs from the other four; the general
+ *             one compacts in place and leaves the fifth unused) -- 1.98 GB for the 1008 x 756 LLFF frame at 256 samples
+ *             (four quarters, 1.59 GB, before).  Always size it with k4_march_workspace_bytes: the layout is the library's
+ *             own, no entry point, structure or argument changed meaning, so the ABI number did not move.
  *   out_rgb [n_rays][3], out_depth [n_rays], out_alphainv [n_rays]
  *   out_counters : NULL or uint64[8] (ABI 12; [4] before) = {in-bbox samples, mask-pass samples, alpha-pass samples,
  *                  shaded samples, alpha-pass samples BEHIND their ray's T<1e-3 stop (density evaluated, then dropped by the
