@@ -1,8 +1,9 @@
 """Checkpoint helpers with the reference's formats (/root/reference/lib/utils.py:50-66).
 
 DVGO/MPI checkpoints: ``{'global_step', 'model_kwargs', 'model_state_dict', 'optimizer_state_dict'}``
-(run_sr.py:1173-1178).  Only what the render / training-step path needs is restated; metrics (SSIM/LPIPS) are out
-of scope.
+(run_sr.py:1173-1178).  Only what the render / training-step path needs is restated.  Frame evaluation: ``rgb_ssim`` with the
+reference's signature (lib/utils.py:88-134) and ``frame_metrics`` (MSE, PSNR and SSIM of a frame pair in one pass) run on the device
+(csrc/k4_metric.hip); LPIPS is out of scope (its linear-layer weights cannot be pinned to their upstream).
 """
 import numpy as np
 import torch
@@ -89,3 +90,117 @@ def model_from_checkpoint_dict(ckpt):
     model = cls(**ckpt['model_kwargs'])
     model.load_state_dict(ckpt['model_state_dict'])
     return model
+
+
+# ---- frame evaluation (csrc/k4_metric.hip) ---------------------------------------------------------------------------
+def ssim_taps(filter_size, filter_sigma):
+    """The 1D Gaussian of lib/utils.py:100-104 as float64, by the reference's own numpy expression (bit for bit: the device sums are
+    held to 1e-10 of the reference's map).  Symmetric for odd and even sizes."""
+    half = filter_size // 2
+    shift = (2 * half - filter_size + 1) / 2
+    taps = np.exp(-0.5 * ((np.arange(filter_size) - half + shift) / filter_sigma)**2)
+    taps /= np.sum(taps)
+    return taps
+
+
+def _metric_image(img, what, channel_last=False):
+    """-> (device fp32 tensor, H, W, pixel stride, channel stride) of a frame given channel-last [H,W,3] or planar [3,H,W] / [1,3,H,W]
+    (any view of either whose rows are dense, e.g. the decoder's [1,3,H,W] view of an NHWC result).  channel_last: the frame came as a numpy
+    array, which is [H,W,3] by the reference's contract; a [3,H,3] TENSOR could be either layout and is refused."""
+    from .. import _native as N
+    if not isinstance(img, torch.Tensor):
+        raise N.K4Error(f'{what}: expected a numpy array or a torch tensor, got {type(img).__name__}')
+    if img.dtype != torch.float32:          # float64 frames would silently change the reference's fp32 rounding of img**2
+        raise N.K4Error(f'{what}: expected float32, got {img.dtype}')
+    if not img.is_cuda:
+        raise N.K4Error(f'{what}: tensor must be on the GPU (no CPU path exists for the frame metrics)')
+    planar = None
+    if img.dim() == 4 and img.shape[0] == 1 and img.shape[1] == 3:          # the four-dimensional form is planar only
+        img, planar = img[0], True
+    if img.dim() != 3:
+        raise N.K4Error(f'{what}: expected [H,W,3], [3,H,W] or [1,3,H,W], got {tuple(img.shape)}')
+    if planar is None:
+        if img.shape[-1] == 3 and img.shape[0] == 3 and not channel_last:
+            raise N.K4Error(f'{what}: a {tuple(img.shape)} tensor is both [H,W,3] and [3,H,W]; pass the planar frame as [1,3,H,W] '
+                            f'or the channel-last one as a numpy array')
+        planar = img.shape[-1] != 3
+    if not planar:                          # channel-last, as the reference asserts (lib/utils.py:95-96)
+        H, W = int(img.shape[0]), int(img.shape[1])
+        sy, sx, sc = img.stride()
+    elif img.shape[0] == 3:
+        H, W = int(img.shape[1]), int(img.shape[2])
+        sc, sy, sx = img.stride()
+    else:
+        raise N.K4Error(f'{what}: expected [H,W,3], [3,H,W] or [1,3,H,W], got {tuple(img.shape)}')
+    if sx < 1 or sc < 1 or (H > 1 and sy != W * sx):
+        raise N.K4Error(f'{what}: rows must be dense (strides {tuple(img.stride())} of shape {tuple(img.shape)})')
+    return img, H, W, int(sx), int(sc)
+
+
+def _frame_metric_sums(img0, img1, clamp0, clamp1, max_val, filter_size, filter_sigma, k1, k2, want_map, channel_last=(False, False)):
+    """One k4_frame_metrics call -> (sums [2] fp64 device tensor: sum of the SSIM map, sum of squared differences; the map or None; H, W)."""
+    from .. import _native as N
+    a, H, W, ps0, cs0 = _metric_image(img0, 'img0', channel_last[0])
+    b, H1, W1, ps1, cs1 = _metric_image(img1, 'img1', channel_last[1])
+    if (H, W) != (H1, W1):
+        raise N.K4Error(f'frames differ in size: {H}x{W} against {H1}x{W1}')
+    if a.device != b.device:
+        raise N.K4Error(f'frames are on different devices: {a.device}, {b.device}')
+    n = int(filter_size)
+    if n < 1 or n > 31:
+        raise N.K4Error(f'filter_size {filter_size} outside [1, 31]')
+    if H < n or W < n:
+        raise N.K4Error(f'a {H}x{W} frame is smaller than the {n}-tap filter')
+    taps = np.ascontiguousarray(ssim_taps(n, filter_sigma), dtype=np.float64)
+    c1, c2 = float((k1 * max_val)**2), float((k2 * max_val)**2)             # lib/utils.py:128-129
+    lib = N.lib()
+    with torch.cuda.device(a.device):
+        ws = torch.empty(int(lib.k4_frame_metrics_workspace_bytes(H, W, n)), dtype=torch.uint8, device=a.device)
+        sums = torch.empty(2, dtype=torch.float64, device=a.device)
+        ssim_map = torch.empty(H - n + 1, W - n + 1, 3, dtype=torch.float64, device=a.device) if want_map else None
+        N.check(lib.k4_frame_metrics(N.C.c_void_p(a.data_ptr()), ps0, cs0, int(bool(clamp0)), N.C.c_void_p(b.data_ptr()), ps1, cs1, int(bool(clamp1)),
+                                     H, W, taps.ctypes.data_as(N.C.POINTER(N.C.c_double)), n, c1, c2,
+                                     N.ptr(ssim_map), N.ptr(ws), N.ptr(sums), N.stream()), 'k4_frame_metrics')
+    return sums, ssim_map, H, W
+
+
+def _to_device_frame(x, device=None):
+    """numpy float32 [H,W,3] -> device tensor (uploaded); tensors pass through."""
+    if isinstance(x, np.ndarray):
+        from .. import _native as N
+        if x.dtype != np.float32:
+            raise N.K4Error(f'expected a float32 frame, got {x.dtype}')
+        if x.ndim != 3 or x.shape[-1] != 3:
+            raise N.K4Error(f'expected a [H,W,3] array, got {x.shape}')
+        return torch.from_numpy(np.ascontiguousarray(x)).to(device if device is not None else 'cuda')
+    return x
+
+
+def rgb_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, return_map=False):
+    """lib/utils.py:88-134 on the device.  numpy float32 [H,W,3] frames are uploaded and the result is numpy (np.float64, or the float64 map):
+    drop-in for run_sr.py:147,1134.  Device float32 tensors (channel-last [H,W,3] or planar [3,H,W] / [1,3,H,W]) give device float64 tensors
+    without a host synchronisation.  Any other dtype, a size mismatch or a frame smaller than the filter raises."""
+    as_numpy = isinstance(img0, np.ndarray) and isinstance(img1, np.ndarray)
+    dev = next((x.device for x in (img0, img1) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    a, b = _to_device_frame(img0, dev), _to_device_frame(img1, dev)
+    sums, ssim_map, H, W = _frame_metric_sums(a, b, False, False, max_val, filter_size, filter_sigma, k1, k2, return_map,
+                                              (isinstance(img0, np.ndarray), isinstance(img1, np.ndarray)))
+    if return_map:
+        return ssim_map.cpu().numpy() if as_numpy else ssim_map
+    ssim = sums[0] / float((H - filter_size + 1) * (W - filter_size + 1) * 3)
+    return np.float64(ssim.item()) if as_numpy else ssim
+
+
+def frame_metrics(pred, gt, max_val=1.0, clamp_pred=False, return_map=False):
+    """{'mse', 'psnr', 'ssim'[, 'ssim_map']} of a frame pair as device float64 tensors from ONE pass over the two frames (what a validation
+    loop computes on the decoder's output, run_sr.py:1131-1134: clamp_pred=True clamps `pred` to [0, 1] in the load).  mse = mean (pred - gt)^2,
+    psnr = 20 log10(max_val) - 10 log10(mse) (run_sr.py:1133 with max_val = 1), ssim = rgb_ssim(pred, gt, max_val) with the default filter."""
+    dev = next((x.device for x in (pred, gt) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    a, b = _to_device_frame(pred, dev), _to_device_frame(gt, dev)
+    sums, ssim_map, H, W = _frame_metric_sums(a, b, clamp_pred, False, max_val, 11, 1.5, 0.01, 0.03, return_map,
+                                              (isinstance(pred, np.ndarray), isinstance(gt, np.ndarray)))
+    mse = sums[1] / float(H * W * 3)
+    out = {'mse': mse, 'psnr': 20. * float(np.log10(max_val)) - 10. * torch.log10(mse), 'ssim': sums[0] / float((H - 10) * (W - 10) * 3)}
+    if return_map:
+        out['ssim_map'] = ssim_map
+    return out

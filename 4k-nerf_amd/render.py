@@ -12,7 +12,7 @@ per-sample intermediates), rays are generated on the device, ONE launch per fram
 import numpy as np
 import torch
 
-from .lib import dvgo
+from .lib import dvgo, utils
 
 
 @torch.no_grad()
@@ -42,14 +42,16 @@ def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs,
                       arr_index=None, img_enc=None):
     '''Render images for the given viewpoints; run evaluation if gt given.'''
     assert len(render_poses) == len(HW) and len(HW) == len(Ks)
-    if eval_ssim or eval_lpips_alex or eval_lpips_vgg:
-        raise NotImplementedError('SSIM/LPIPS evaluation is outside the hot-path scope (SURVEY.md 2.1 #17)')
+    if eval_lpips_alex or eval_lpips_vgg:
+        raise NotImplementedError("LPIPS evaluation needs the `lpips` package's linear-layer weights, which are not available: "
+                                  'nothing of it could be pinned to its upstream (SSIM: eval_ssim=True)')
     if render_factor != 0:
         HW = np.copy(HW)
         Ks = np.copy(Ks)
         HW = (HW / render_factor).astype(int)
         Ks[:, :2, :3] /= render_factor
     rgbs, rgb_features, depths, bgmaps, psnrs, viewdirs_all = [], [], [], [], [], []
+    ssims = []
     for i, c2w in enumerate(render_poses):
         H, W = int(HW[i][0]), int(HW[i][1])
         K = Ks[i]
@@ -67,6 +69,11 @@ def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs,
         viewdirs_all.append(rays[2].flatten(0, -2))
         if gt_imgs is not None and render_factor == 0:
             psnrs.append(-10. * np.log10(np.mean(np.square(rgb - gt_imgs[i]))))
+            if eval_ssim:       # run_sr.py:146-147 on the device: the frame is clamped in the kernel's load, the value stays there until the loop is done
+                gt = gt_imgs[i] if isinstance(gt_imgs[i], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_imgs[i]))
+                ssims.append(utils.frame_metrics(res['rgb_marched'], gt.to(dev), max_val=1, clamp_pred=True)['ssim'])
+    if len(psnrs) and eval_ssim:
+        print('Testing ssim', np.mean([float(s) for s in ssims]), '(avg)')          # run_sr.py:155
     if render_video_flipy:
         for i in range(len(rgbs)):
             rgbs[i], depths[i], bgmaps[i] = np.flip(rgbs[i], 0), np.flip(depths[i], 0), np.flip(bgmaps[i], 0)

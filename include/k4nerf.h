@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      18      /* 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      19      /* 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -868,6 +868,28 @@ int k4_vgg_l1_bwd(const float* a, const float* b, int64_t n, float scale, const 
 int64_t k4_vgg_gram_workspace_bytes(int32_t n_pix, int32_t channels);
 int k4_vgg_gram(const float* f, int32_t n_pix, int32_t channels, float* workspace, int64_t workspace_bytes, float* gram, void* stream);
 int k4_vgg_gram_bwd_pack(const float* gram, int32_t n_pix, int32_t channels, float scale, const float* grad_loss, void* w_split, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Frame evaluation (csrc/k4_metric.hip): SSIM and the squared-difference sum of two device-resident frames in one pass.
+ * Replaces utils.rgb_ssim (lib/utils.py:88-134: ten scipy.signal.convolve2d passes per channel on the host) and the host
+ * np.mean(np.square(rgb - gt)) of run_sr.py:144,1132 wherever run_sr.py scores a frame (run_sr.py:147,1134).
+ * k4_frame_metrics: img0, img1 fp32 frames of H x W x 3 with dense rows; element (y, x, c) of an image is at
+ *   c * channel_stride + (y * W + x) * pixel_stride (elements): [H][W][3] is (3, 1), planar [3][H][W] is (1, H * W); the two images may differ.
+ *   clamp0 / clamp1 != 0: the image is clamped to [0, 1] in the load (torch.clamp: NaN kept; run_sr.py:130,1131 clamp before the metrics).
+ *   taps: n_taps fp64 values in HOST memory (copied into the launch), the 1D filter of lib/utils.py:100-104; n_taps in [1, 31]; the table is
+ *   symmetric, so correlation equals convolution.  c1 = (k1 * max_val)^2, c2 = (k2 * max_val)^2 (lib/utils.py:128-129).
+ *   Arithmetic as the reference: fp32 products img0**2, img1**2, img0*img1 (lib/utils.py:118-120), every filtered sum in fp64 ('valid', vertical pass
+ *   first, lib/utils.py:110-112), the clips of lib/utils.py:124-127 with numpy's NaN propagation, the quotient of lib/utils.py:130-132.
+ *   ssim_map (may be NULL: nothing per pixel is written) fp64 [H - n_taps + 1][W - n_taps + 1][3]; sums [2] fp64 on the device: sums[0] = the sum of the
+ *   map (lib/utils.py:133 divides by its size), sums[1] = sum (img0 - img1)^2 of the (clamped) images, fp32 squares added in fp64.  Both are added in a fixed
+ *   order (workgroup partials in `workspace`, k4_frame_metrics_workspace_bytes(H, W, n_taps) bytes, then index order): two calls give the same bits; no
+ *   host synchronisation.  H < n_taps, W < n_taps, n_taps > 31, H * W * 3 >= 2^31 or 3 * W + 256 >= 2^31: K4_ERR_UNSUPPORTED (the workspace size is then -1).  Recordable on a launch tape.
+ * ------------------------------------------------------------------------------------------- */
+int64_t k4_frame_metrics_workspace_bytes(int32_t H, int32_t W, int32_t n_taps);
+int k4_frame_metrics(const float* img0, int64_t pixel_stride0, int64_t channel_stride0, int32_t clamp0,
+                     const float* img1, int64_t pixel_stride1, int64_t channel_stride1, int32_t clamp1,
+                     int32_t H, int32_t W, const double* taps, int32_t n_taps, double c1, double c2,
+                     double* ssim_map, void* workspace, double* sums, void* stream);
 
 #ifdef __cplusplus
 }
