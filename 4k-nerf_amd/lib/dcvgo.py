@@ -299,7 +299,7 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
             d.bg_len = float(self.bg_len)
             d.dist_thres = float((2 + 2 * self.bg_len) / self.world_len * stepsize * 0.95)        # lib/dcvgo.py:300
             d.norm_l2 = int(self.contracted_norm == 'l2')
-            dens, k0 = self.density.grid.detach().contiguous(), self.k0.grid.detach().contiguous()
+            dens, k0 = self._k4_dense(self.density).detach().contiguous(), self._k4_dense(self.k0).detach().contiguous()
             mc = self.mask_cache
             mask = mc.mask.contiguous()
             d.density, d.k0, d.k0_ch = dens.data_ptr(), k0.data_ptr(), int(k0.shape[1])

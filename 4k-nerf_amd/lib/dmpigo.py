@@ -276,7 +276,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         version): the multiple of 64 samples behind which the largest share of alpha-passing voxels sits in columns already stopped, if that
         share is at least DEPTH_SPLIT_MIN_GAIN and at least DEPTH_SPLIT_MIN_OPAQUE of the occupied columns stop a ray at all (a scene of opaque
         surfaces, as a trained LLFF scene is) -- translucent scenes keep the single launch (0).  Identical outputs either way (tests)."""
-        dens, act = self.density.grid, self.act_shift.grid
+        dens, act = self._k4_dense(self.density), self.act_shift.grid
         key = ('dsplit', dens.data_ptr(), dens._version, act.data_ptr(), act._version, float(interval), float(self.fast_color_thres), int(n_samples))
         c = self._k4_cache()
         if c.get('dsplit_key') != key:
@@ -334,6 +334,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         Nr = len(rays_o)
         interval = stepsize * self.voxel_size_ratio
         presel = (_TRAIN_PRESEL if k4_presel is None else bool(k4_presel)) and self.mask_cache is not None and self.fast_color_thres > 0
+        presel = presel and isinstance(self.density, grid.DenseGrid)      # (the selection kernel reads a dense density; a factored one takes the filter-by-filter form)
         if presel:
             assert near == 0 and far == 1
             N_samples = int((self.mpi_depth - 1) / stepsize) + 1

@@ -55,11 +55,26 @@ class _FusedMarcher:
                 and lins[-1].out_features == 3 and getattr(self, 'mode_type', 'mlp') not in ('TRANS', 'adain')
                 and not getattr(self, 'rgbnet_full_implicit', False))
 
+    def _k4_dense(self, g):
+        """The [1,C,X,Y,Z] tensor the fused kernels read for grid module `g`.  A DenseGrid: its parameter itself (the same tensor, hence the same cache keys
+        and the same bits as ever).  A TensoRFGrid: its dense expansion (k4_tensorf_dense), cached on the factor parameters' (data_ptr, version) -- trilinear
+        interpolation of sum_r plane_r (x) vec_r equals the factored lookup in real arithmetic, so the fused marcher renders factored scenes at its usual
+        rate, at the price of a dense copy while rendering."""
+        if not isinstance(g, grid.TensoRFGrid):
+            return g.grid
+        c = self._k4_cache()
+        slot = ('dense', id(g))
+        key = g.factor_key()
+        hit = c.get(slot)
+        if hit is None or hit[0] != key:
+            hit = c[slot] = (key, g.get_dense_grid())
+        return hit[1]
+
     def _k4_k0_channel_last(self):
-        """Load-time repack of k0.grid [1,C,X,Y,Z] -> [X,Y,Z,CP] (CP = C rounded up to 4): the 8 corners of a
+        """Load-time repack of the k0 grid [1,C,X,Y,Z] -> [X,Y,Z,CP] (CP = C rounded up to 4): the 8 corners of a
         shaded sample become 4 runs of 2*CP contiguous floats instead of 8*C scattered dwords.
         Returns (repacked grid, CP, k4_grid_desc.k0_layout)."""
-        g = self.k0.grid
+        g = self._k4_dense(self.k0)
         key = ('k0', g.data_ptr(), g._version, str(g.device))
         c = self._k4_cache()
         if c.get('k0_key') != key:
@@ -92,7 +107,7 @@ class _FusedMarcher:
         (k4_build_live_mask): the geometry kernel looks samples up in THIS mask, so the density stage no longer runs on samples that
         the reference drops one step later at lib/dmpigo.py:319-323 / lib/dvgo.py:356-360.  Bit-identical outputs; cached per
         density / act_shift / mask version and per (shift, interval, threshold).  Returns (live mask, its coarse summary)."""
-        dens, m = self.density.grid, self.mask_cache.mask
+        dens, m = self._k4_dense(self.density), self.mask_cache.mask
         key = ('live', dens.data_ptr(), dens._version, m.data_ptr(), m._version, str(m.device), float(shift), float(interval),
                float(self.fast_color_thres)) + ((act_shift_grid.data_ptr(), act_shift_grid._version) if act_shift_grid is not None else ())
         c = self._k4_cache()
@@ -175,13 +190,13 @@ class _FusedMarcher:
         instead of mask_cache.mask -- the render path; None: the MaskGrid itself (sample counters, fast_color_thres == 0)."""
         gd = N.GridDesc()
         self._k4_params_ready()
-        dens = self.density.grid
+        dens = self._k4_dense(self.density)
         k0cl, cpad, k0_layout = self._k4_k0_channel_last()
         gd.density = dens.data_ptr()
         gd.k0 = k0cl.data_ptr()
         gd.k0_layout = k0_layout
         gd.k0_cpad = cpad
-        gd.k0_ch = self.k0.grid.shape[1]
+        gd.k0_ch = self._k4_dense(self.k0).shape[1]
         gd.dims = (N.C.c_int32 * 3)(*[int(v) for v in dens.shape[2:]])
         if act_shift_grid is not None:
             gd.act_shift = act_shift_grid.data_ptr()
@@ -212,7 +227,7 @@ class _FusedMarcher:
         ``build()`` -> (value, tensors to keep alive).  A plan is valid per HIP stream it was built or re-validated on: the first call on
         another stream goes through ``build`` again, which orders that stream behind the load-time kernels (see _k4_live_mask)."""
         mc = self.mask_cache
-        ts = [self.density.grid, self.k0.grid, mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
+        ts = [self._k4_dense(self.density), self._k4_dense(self.k0), mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
         act = getattr(self, 'act_shift', None)
         ts.append(act.grid if isinstance(act, nn.Module) else act)
         if self.rgbnet is not None:
@@ -229,7 +244,7 @@ class _FusedMarcher:
     def _k4_versions_key(self):
         """(storage, version) of every tensor the fused path's load-time state is derived from (see _k4_plan)."""
         mc = self.mask_cache
-        ts = [self.density.grid, self.k0.grid, mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
+        ts = [self._k4_dense(self.density), self._k4_dense(self.k0), mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
         act = getattr(self, 'act_shift', None)
         ts.append(act.grid if isinstance(act, nn.Module) else act)
         if self.rgbnet is not None:
@@ -417,6 +432,8 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
     @torch.no_grad()
     def maskout_near_cam_vox(self, cam_o, near_clip):
         """lib/dvgo.py:186-198: density = -100 at grid nodes closer than `near_clip` to any camera centre."""
+        if not hasattr(self.density, 'grid'):
+            raise NotImplementedError(f'maskout_near_cam_vox writes density.grid: not available for a {type(self.density).__name__} density (as upstream)')
         nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
         cam_o = cam_o.to(nodes.device)
         nearest = torch.stack([(nodes.unsqueeze(-2) - co).pow(2).sum(-1).sqrt().amin(-1) for co in cam_o.split(100)]).amin(0)

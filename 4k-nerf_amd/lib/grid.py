@@ -3,9 +3,11 @@
 ``DenseGrid`` (lib/grid.py:108-151) and ``MaskGrid`` (lib/grid.py:274-307) keep constructor
 arguments, parameter / buffer names (``grid``, ``xyz_min``, ``xyz_max``, ``mask``, ``xyz2ijk_scale``,
 ``xyz2ijk_shift``) and forward semantics; the lookups run on the gfx950 kernels of lib4k_hip.so.
-``TensoRFGrid`` / ``VQGrid`` are not selected by any BASELINE configuration
-(configs/default.py:85-86) and are out of the hot-path scope.
+``TensoRFGrid`` (lib/grid.py:157-268): the vector-matrix factored grid, its lookup / backward / dense expansion / total variation on the
+kernels of csrc/k4_tensorf.hip.  ``VQGrid`` is not selected by any configuration (configs/default.py:85-86) and is not provided.
 """
+
+import math
 
 import torch
 import torch.nn as nn
@@ -330,7 +332,9 @@ class GridGrad:
 def create_grid(type, **kwargs):
     if type == 'DenseGrid':
         return DenseGrid(**kwargs)
-    raise NotImplementedError(f'{type}: only DenseGrid is on the 4K-NeRF hot path (SURVEY.md 2.1 #6)')
+    if type == 'TensoRFGrid':
+        return TensoRFGrid(**kwargs)
+    raise NotImplementedError(f'{type}: only DenseGrid and TensoRFGrid are provided (SURVEY.md 2.1 #6)')
 
 
 class DenseGrid(nn.Module):
@@ -462,6 +466,148 @@ class DenseGrid(nn.Module):
     def extra_repr(self):
         ws = self.world_size.tolist() if torch.is_tensor(self.world_size) else list(self.world_size)
         return f'channels={self.channels}, world_size={ws}'
+
+
+
+_TENSORF_FACTORS = ('xy_plane', 'xz_plane', 'yz_plane', 'x_vec', 'y_vec', 'z_vec')
+
+
+def _tensorf_args(factors, f_vec, channels, world):
+    """The factor pointers and sizes every k4_tensorf_* entry point takes (include/k4nerf.h), from contiguous fp32 device tensors in checkpoint layout."""
+    xy, xz, yz = factors[:3]
+    X, Y, Z = world
+    shapes = ((1, xy.shape[1], X, Y), (1, xz.shape[1], X, Z), (1, xz.shape[1], Y, Z), (1, xz.shape[1], X, 1), (1, xz.shape[1], Y, 1), (1, xy.shape[1], Z, 1))
+    for name, t, want in zip(_TENSORF_FACTORS, factors, shapes):
+        if tuple(t.shape) != want:
+            raise N.K4Error(f'TensoRFGrid: {name} is {tuple(t.shape)}, expected {want}')
+    if channels > 1 and tuple(f_vec.shape) != (xy.shape[1] + 2 * xz.shape[1], channels):
+        raise N.K4Error(f'TensoRFGrid: f_vec is {tuple(f_vec.shape)}, expected {(xy.shape[1] + 2 * xz.shape[1], channels)}')
+    return [N.f32(t) for t in factors] + [N.f32(f_vec) if channels > 1 else None, channels, xz.shape[1], xy.shape[1], X, Y, Z]
+
+
+def _tensorf_fwd(factors, f_vec, channels, world, pts, xyz_min, xyz_max):
+    out = torch.empty([pts.shape[0], channels], dtype=torch.float32, device=pts.device)
+    N.check(N.lib().k4_tensorf_sample(*_tensorf_args(factors, f_vec, channels, world), N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), pts.shape[0],
+                                      N.f32(out), N.stream()), 'k4_tensorf_sample')
+    return out
+
+
+class TensoRFSample(torch.autograd.Function):
+    """TensoRFGrid lookup with a HIP backward (k4_tensorf_sample_backward): gradients of the six factors and f_vec, the interpolated values recomputed from the
+    points; none w.r.t. the points (they come from rays).  Float-atomic sums: not bitwise reproducible from run to run."""
+
+    @staticmethod
+    def forward(ctx, pts, xyz_min, xyz_max, channels, world, f_vec, *factors):
+        factors = [f.detach().contiguous() for f in factors]
+        f_vec = f_vec.detach().contiguous() if channels > 1 else None
+        ctx.save_for_backward(pts, xyz_min, xyz_max, *factors, *([f_vec] if channels > 1 else []))
+        ctx.channels, ctx.world = channels, world
+        return _tensorf_fwd(factors, f_vec, channels, world, pts, xyz_min, xyz_max)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pts, xyz_min, xyz_max, *rest = ctx.saved_tensors
+        factors, f_vec = rest[:6], rest[6] if ctx.channels > 1 else None
+        go = grad_out.float().contiguous()
+        grads = [torch.zeros_like(f) for f in factors]
+        g_f = torch.zeros_like(f_vec) if f_vec is not None else None
+        N.check(N.lib().k4_tensorf_sample_backward(N.f32(go), *_tensorf_args(factors, f_vec, ctx.channels, ctx.world), N.f32(pts), N.f32(xyz_min), N.f32(xyz_max),
+                                                   pts.shape[0], *[N.f32(g) for g in grads], N.f32(g_f) if g_f is not None else None, N.stream()),
+                'k4_tensorf_sample_backward')
+        return (None, None, None, None, None, g_f, *grads)
+
+
+class TensoRFGrid(nn.Module):
+    """Vector-matrix factored grid (TensoRF, arXiv:2203.09517; lib/grid.py:157-268): constructor, parameter / buffer names, initial distributions and
+    semantics of the reference; lookup, backward, dense expansion and total variation on csrc/k4_tensorf.hip, resize on k4_resample_trilinear."""
+
+    def __init__(self, channels, world_size, xyz_min, xyz_max, config):
+        super().__init__()
+        self.channels, self.world_size, self.config = channels, world_size, config
+        for name, val in (('xyz_min', xyz_min), ('xyz_max', xyz_max)):
+            self.register_buffer(name, _vec3(val))
+        X, Y, Z = [int(v) for v in world_size]
+        R = config['n_comp']
+        Rxy = config.get('n_comp_xy', R)
+        self.xy_plane = nn.Parameter(torch.randn([1, Rxy, X, Y]) * 0.1)
+        self.xz_plane = nn.Parameter(torch.randn([1, R, X, Z]) * 0.1)
+        self.yz_plane = nn.Parameter(torch.randn([1, R, Y, Z]) * 0.1)
+        self.x_vec = nn.Parameter(torch.randn([1, R, X, 1]) * 0.1)
+        self.y_vec = nn.Parameter(torch.randn([1, R, Y, 1]) * 0.1)
+        self.z_vec = nn.Parameter(torch.randn([1, Rxy, Z, 1]) * 0.1)
+        if self.channels > 1:
+            self.f_vec = nn.Parameter(torch.ones([R + R + Rxy, channels]))
+            nn.init.kaiming_uniform_(self.f_vec, a=math.sqrt(5))
+
+    def factors(self):
+        return [getattr(self, name) for name in _TENSORF_FACTORS]
+
+    def _world(self):
+        return (self.xy_plane.shape[2], self.xy_plane.shape[3], self.xz_plane.shape[3])
+
+    def _device_factors(self, what):
+        fs = [f.detach().contiguous() for f in self.factors()]
+        fv = self.f_vec.detach().contiguous() if self.channels > 1 else None
+        if not fs[0].is_cuda:
+            raise N.K4Error(f'TensoRFGrid.{what}: the grid must be on the GPU (no CPU path)')
+        return fs, fv
+
+    def forward(self, xyz):
+        """The six bilinear lookups, their products and the f_vec product of lib/grid.py:178-196, 241-268 in one kernel (k4_tensorf_sample); under autograd
+        the backward is k4_tensorf_sample_backward."""
+        shape = xyz.shape[:-1]
+        pts = xyz.reshape(-1, 3).contiguous()
+        if not pts.is_cuda or not self.xy_plane.is_cuda:
+            raise N.K4Error('TensoRFGrid.forward: points and grid must be on the GPU (no CPU path)')
+        params = self.factors() + ([self.f_vec] if self.channels > 1 else [])
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            out = TensoRFSample.apply(pts.detach(), self.xyz_min, self.xyz_max, self.channels, self._world(),
+                                      self.f_vec if self.channels > 1 else None, *self.factors())
+        else:
+            fs, fv = self._device_factors('forward')
+            out = _tensorf_fwd(fs, fv, self.channels, self._world(), pts, self.xyz_min, self.xyz_max)
+        return out.reshape(*shape, self.channels) if self.channels > 1 else out.reshape(*shape)
+
+    def scale_volume_grid(self, new_world_size):
+        """F.interpolate(bilinear, align_corners=True) of each factor (lib/grid.py:198-207) on k4_resample_trilinear with size-1 trailing axes: there the
+        kernel's z weights are exactly (1, 0), which leaves torch's bilinear expression.  New parameters, as upstream."""
+        if self.channels == 0:
+            return
+        X, Y, Z = [int(v) for v in new_world_size]
+        fs, _ = self._device_factors('scale_volume_grid')
+        for name, src, (a, b) in zip(_TENSORF_FACTORS, fs, ((X, Y), (X, Z), (Y, Z), (X, 1), (Y, 1), (Z, 1))):
+            data = torch.empty([1, src.shape[1], a, b], dtype=torch.float32, device=src.device)
+            N.check(N.lib().k4_resample_trilinear(N.f32(src), src.shape[1], src.shape[2], src.shape[3], 1, N.f32(data), a, b, 1, N.stream()), 'k4_resample_trilinear')
+            setattr(self, name, nn.Parameter(data))
+        self.world_size = new_world_size
+
+    def total_variation_add_grad(self, wx, wy, wz, dense_mode=None):
+        """lib/grid.py:209-221 without autograd: the smooth-L1 (beta 1, summed) total variation of the six factors, weighted per axis, / 6, added to ``.grad``
+        (created when missing).  f_vec gets nothing; `dense_mode` is ignored, as upstream."""
+        fs, _ = self._device_factors('total_variation_add_grad')
+        for p, src, (wa, wb) in zip(self.factors(), fs, ((wx, wy), (wx, wz), (wy, wz), (wx, 0.), (wy, 0.), (wz, 0.))):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            N.check(N.lib().k4_tensorf_tv_add_grad(N.f32(src), N.f32(p.grad), src.shape[1], src.shape[2], src.shape[3], float(wa), float(wb), N.stream()),
+                    'k4_tensorf_tv_add_grad')
+
+    @torch.no_grad()
+    def get_dense_grid(self):
+        """[1, C, X, Y, Z] = sum_r plane_r (x) vec_r (times f_vec) of lib/grid.py:223-236 (k4_tensorf_dense)."""
+        fs, fv = self._device_factors('get_dense_grid')
+        X, Y, Z = self._world()
+        out = torch.empty([1, self.channels, X, Y, Z], dtype=torch.float32, device=fs[0].device)
+        N.check(N.lib().k4_tensorf_dense(*_tensorf_args(fs, fv, self.channels, (X, Y, Z)), N.f32(out), N.stream()), 'k4_tensorf_dense')
+        return out
+
+    def factor_key(self):
+        """(data_ptr, version) of every factor parameter: what a cached dense expansion is keyed on."""
+        return tuple((p.data_ptr(), p._version) for p in self.factors() + ([self.f_vec] if self.channels > 1 else []))
+
+    def extra_repr(self):
+        ws = self.world_size.tolist() if torch.is_tensor(self.world_size) else list(self.world_size)
+        return f'channels={self.channels}, world_size={ws}, n_comp={self.config["n_comp"]}'
 
 
 def _mask_from_coarse_checkpoint(path, thres):

@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      19      /* 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      20      /* 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -890,6 +890,33 @@ int k4_frame_metrics(const float* img0, int64_t pixel_stride0, int64_t channel_s
                      const float* img1, int64_t pixel_stride1, int64_t channel_stride1, int32_t clamp1,
                      int32_t H, int32_t W, const double* taps, int32_t n_taps, double c1, double c2,
                      double* ssim_map, void* workspace, double* sums, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 20 -- vector-matrix factored grids (csrc/k4_tensorf.hip): TensoRFGrid of lib/grid.py:157-268.
+ * Factors in checkpoint layout, fp32: planes xy [Rxy][X][Y], xz [R][X][Z], yz [R][Y][Z]; vectors xv [R][X], yv [R][Y], zv [Rxy][Z];
+ * fvec [Rxy + 2R][C] (rows: the xy*z products, then xz*y, then yz*x), NULL when C == 1.
+ * k4_tensorf_sample: out [n][C].  Coordinates as k4_grid_sample_3d (a point falls in the same cell); each of the six lookups is
+ *   F.grid_sample(bilinear, align_corners=True, zero padding) on its own, a vector's size-1 axis resolving to index 0 with weight 1.
+ *   C == 1: sum_r xy*zv + sum_r xz*yv + sum_r yz*xv.  C > 1: that [Rxy + 2R] vector of products times fvec.  C <= 32.
+ * k4_tensorf_sample_backward: ACCUMULATES the gradients of all factors (g_fvec NULL when C == 1) for grad_out [n][C]; the six interpolated
+ *   values are recomputed from the points, nothing of size [n][R] reaches memory.  Planes: fp32 atomics into the gradient.  Vectors: per-workgroup
+ *   sums in LDS flushed once per workgroup while they fit (144 KB together with the fvec sums), else fp32 atomics.  fvec: workgroup sums in LDS;
+ *   (Rxy + 2R) * C > 8192: K4_ERR_UNSUPPORTED.  Float-atomic sums: not bitwise reproducible from run to run.  No gradient for the points.
+ * k4_tensorf_dense: get_dense_grid (lib/grid.py:223-236), out [C][X][Y][Z].
+ * k4_tensorf_tv_add_grad: one factor [R][A][B] (a vector: B == 1) of total_variation_add_grad (lib/grid.py:209-221) without autograd:
+ *   grad += d/dparam of (wa * sum smooth_l1(p[a+1] - p[a]) + wb * sum smooth_l1(p[b+1] - p[b])) / 6, beta = 1.
+ * n == 0: no launch.
+ * ------------------------------------------------------------------------------------------- */
+int k4_tensorf_sample(const float* xy, const float* xz, const float* yz, const float* xv, const float* yv, const float* zv, const float* fvec,
+                      int32_t C, int32_t R, int32_t Rxy, int32_t X, int32_t Y, int32_t Z,
+                      const float* xyz, const float* xyz_min, const float* xyz_max, int64_t n, float* out, void* stream);
+int k4_tensorf_sample_backward(const float* grad_out, const float* xy, const float* xz, const float* yz, const float* xv, const float* yv,
+                               const float* zv, const float* fvec, int32_t C, int32_t R, int32_t Rxy, int32_t X, int32_t Y, int32_t Z,
+                               const float* xyz, const float* xyz_min, const float* xyz_max, int64_t n,
+                               float* g_xy, float* g_xz, float* g_yz, float* g_xv, float* g_yv, float* g_zv, float* g_fvec, void* stream);
+int k4_tensorf_dense(const float* xy, const float* xz, const float* yz, const float* xv, const float* yv, const float* zv, const float* fvec,
+                     int32_t C, int32_t R, int32_t Rxy, int32_t X, int32_t Y, int32_t Z, float* out, void* stream);
+int k4_tensorf_tv_add_grad(const float* param, float* grad, int32_t R, int32_t A, int32_t B, float wa, float wb, void* stream);
 
 #ifdef __cplusplus
 }
