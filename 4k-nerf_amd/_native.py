@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 20
+K4_ABI_VERSION = 21
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -39,6 +39,19 @@ class ContractedDesc(C.Structure):     # k4_contracted_desc (ABI 15)
                 ('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p), ('w3', C.c_void_p), ('b3', C.c_void_p),
                 ('dim0', C.c_int32), ('width', C.c_int32), ('n_hidden', C.c_int32), ('viewfreq', C.c_void_p), ('n_pe', C.c_int32),
                 ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_last', C.c_void_p), ('counters', C.c_void_p)]
+
+
+class BivoxDesc(C.Structure):          # k4_bivox_desc (ABI 21)
+    _fields_ = [('rays_o', C.c_void_p), ('rays_d', C.c_void_p), ('viewdirs', C.c_void_p), ('n_rays', C.c_int64),
+                ('scene_center', C.c_float * 3), ('scene_radius', C.c_float * 3),
+                ('stepdist', C.c_float), ('far', C.c_float), ('bg_preserve', C.c_float), ('n_outer', C.c_int32),
+                ('act_shift', C.c_float), ('interval', C.c_float), ('fast_color_thres', C.c_float), ('bg', C.c_float),
+                ('xyz_min', C.c_void_p), ('xyz_max', C.c_void_p),
+                ('density', C.c_void_p * 2), ('k0', C.c_void_p * 2), ('k0_ch', C.c_int32 * 2), ('dims', (C.c_int32 * 3) * 2),
+                ('mask', C.c_void_p * 2), ('mask_dims', (C.c_int32 * 3) * 2), ('xyz2ijk_scale', C.c_void_p * 2), ('xyz2ijk_shift', C.c_void_p * 2),
+                ('w1', C.c_void_p * 2), ('b1', C.c_void_p * 2), ('w2', C.c_void_p * 2), ('b2', C.c_void_p * 2), ('w3', C.c_void_p * 2), ('b3', C.c_void_p * 2),
+                ('dim0', C.c_int32 * 2), ('width', C.c_int32 * 2), ('n_hidden', C.c_int32 * 2), ('viewfreq', C.c_void_p), ('n_pe', C.c_int32),
+                ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_fg', C.c_void_p), ('alphainv_bg', C.c_void_p), ('counters', C.c_void_p)]
 
 
 class MlpDesc(C.Structure):
@@ -117,6 +130,7 @@ _SIGS = {
     'k4_get_rays_of_a_view': [_I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P],
     'k4_to8b': [_P, _I64, _P, _P],
     'k4_cumdist_thres': [_P, _I64, _I64, _F, _P, _P],
+    'k4_sample_bg_pts_on_rays': [_P, _P, _P, _F, _I32, _I64, _P, _P],
     'k4_repack_k0': [_P, _I32, _I32, _I64, _P, _P],
     'k4_train_select_mpi': [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P, _I32, _F, _F, _P, _P, _P, _P, _P],
     'k4_train_compact': [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P],
@@ -221,6 +235,7 @@ _EXTRA_SIGS = {
     'k4_joint_losses_bwd': ([_P, _P, _P, _P, _P, _P, _P], C.c_int),
     'k4_distortion_loss': ([_P, _P, _P, _I64, _I64, _F, _P, _P, _P], C.c_int),
     'k4_march_contracted_fwd': ([C.POINTER(ContractedDesc), _P], C.c_int),
+    'k4_march_bivox_fwd': ([C.POINTER(BivoxDesc), _P], C.c_int),
     'k4_nhwc_window_to_planar': ([_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P], C.c_int),
     'k4_tape_begin': ([_P], C.c_void_p),
     'k4_tape_end': ([_P], C.c_int),

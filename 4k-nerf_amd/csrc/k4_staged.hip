@@ -1315,6 +1315,280 @@ extern "C" int k4_march_contracted_fwd(const k4_contracted_desc* g, void* stream
     }
     return k4_check_launch();
 }
+// ---------------------------------------------------------------- sample_bg_pts_on_rays (.cu:301-340): DirectBiVoxGO's inverse-sphere background samples
+// The source's arithmetic as written: its `1.` literals make `t_inner - 1. + 1. / (1. - (float)i_step / N_samples)` and
+// `R*R/(t*t) * (1.-bg_preserve) + R/t * bg_preserve` evaluate in fp64 (the fp32 sub-expressions first, in fp32) before the assignment to float rounds
+// them; o + d t and the sum of squares contract to FMAs as in the other samplers.  One expression tree for the staged kernel and the fused marcher.
+__device__ __forceinline__ void k4s_bg_point(const float* __restrict__ o, const float* __restrict__ d, float t_inner, float bg_preserve, int step,
+                                             int n_samples, float (&p)[3]) {
+    const float frac = (float)step / (float)n_samples;
+    const float t = (float)(((double)t_inner - 1.) + 1. / (1. - (double)frac));
+    const float x = fmaf(d[0], t, o[0]), y = fmaf(d[1], t, o[1]), z = fmaf(d[2], t, o[2]);
+    const float tn = sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
+    const float m = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
+    const float R = tn / m;
+    const float a = R * R / (tn * tn);
+    const float b = R / tn * bg_preserve;
+    const float sc = (float)((double)a * (1. - (double)bg_preserve) + (double)b);
+    p[0] = x * sc; p[1] = y * sc; p[2] = z * sc;
+}
+__global__ void k_sample_bg(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ tmax, float bg_preserve,
+                            int n_samples, int64_t n_rays, float* __restrict__ pts) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_rays * n_samples) return;
+    const int64_t ray = idx / n_samples;
+    const int step = (int)(idx % n_samples);
+    float p[3];
+    k4s_bg_point(o + ray * 3, d + ray * 3, tmax[ray], bg_preserve, step, n_samples, p);
+    pts[idx * 3 + 0] = p[0]; pts[idx * 3 + 1] = p[1]; pts[idx * 3 + 2] = p[2];
+}
+extern "C" int k4_sample_bg_pts_on_rays(const float* o, const float* d, const float* tmax, float bg_preserve, int32_t n_samples, int64_t n_rays,
+                                        float* pts, void* stream) {
+    REQ(n_rays >= 0 && n_samples >= 0);
+    if (n_rays == 0 || n_samples == 0) return K4_OK;
+    REQ(o && d && tmax && pts);
+    REQ(n_rays * (int64_t)n_samples <= (int64_t)0x7fffffff * K4_THREADS);
+    hipLaunchKernelGGL(k_sample_bg, dim3(k4_blocks(n_rays * n_samples)), dim3(K4_THREADS), 0, ST, o, d, tmax, bg_preserve, n_samples, n_rays, pts);
+    return k4_check_launch();
+}
+
+// ---------------------------------------------------------------- DirectBiVoxGO inference: ONE launch per call (k4_march_bivox_fwd)
+// The staged forward (lib/dbvgo.py) builds the foreground sample list (one host synchronisation for its length), an [N][N_outer][3] background table,
+// filters each up to three times (a synchronisation per filter) and sums per ray.  Here one WAVE walks one ray through both passes, lanes = 64
+// consecutive steps in depth order, in the shape of k_march_contracted above and on its helpers:
+//   foreground  o' = (o - c) / r, d' = d / |d| (each op rounded once, as the tensor expressions of sample_ray); aabb_t / n_steps_of / the start and
+//               direction of k_pts_fill; p_k = fma(dir, stepdist k, start); bbox test; mask_cache[0]; density[0] -> k4s_raw2alpha -> alpha > thres; the
+//               exact transmittance product of k_alpha2weight incl. the T < 1e-3 stop; w > thres; survivors queued in LDS and shaded 64 at a time
+//               (k4c_shade with grid 0's k0 / rgbnet)
+//   background  only when T_fg > thres: p_k = k4s_bg_point(o', d', t_max, k of n_outer); mask_cache[1]; density[1]; the same filters and product;
+//               k4c_shade with grid 1's k0 / rgbnet (WIDTH 0: sigmoid(k0))
+//   per pass    sum w rgb, sum w k, T, the last kept step (thres == 0: every in-mask sample is kept, also behind the stop -- lib/dbvgo.py:273,283)
+//   compose     lib/dbvgo.py:357-359,392-394, every op rounded once as the tensor expressions are.
+// Each grid's pointers travel in a K4ContractedArgs (the fields the lookups and k4c_shade read), so both passes run the contracted kernel's shading code.
+struct K4BivoxArgs {
+    K4ContractedArgs ph[2];
+    const float *ro, *rd, *vd; int64_t n_rays;
+    float cx, cy, cz, rx, ry, rz, stepdist, far, bg_preserve; int n_outer;
+    float act_shift, interval, thres, bg;
+    float *rgb, *depth, *ainv_fg, *ainv_bg; unsigned long long* counters;
+};
+struct K4BivoxRay { float o[3], d[3], vd[3], start[3], dir[3], t_max; };
+
+// one pass of one ray: -> T, sum[0..2] = sum w rgb, sum[3] = sum w k (valid in lane 0), last = the last kept step or -1 (all lanes), cnt (wave-uniform)
+template <int WIDTH, bool BG>
+__device__ __forceinline__ void k4b_pass(const K4BivoxArgs& A, const K4ContractedArgs& G, const K4BivoxRay& R, int n_steps, int lane, int* qk, float* qw,
+                                         float& T_out, float (&sum)[4], int& last, unsigned long long (&cnt)[4]) {
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const bool count = A.counters != nullptr;
+    const bool filt = A.thres > 0.f;
+    auto point = [&](int k, float (&p)[3]) {
+        if (BG) k4s_bg_point(R.o, R.d, R.t_max, A.bg_preserve, k, A.n_outer, p);
+        else {
+            const float dist = A.stepdist * (float)k;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) p[a] = fmaf(R.dir[a], dist, R.start[a]);
+        }
+    };
+    float T = 1.f;
+    bool stopped = false;
+    int nq = 0, my_last = -1;
+    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
+    unsigned long long c_pre = 0, c_mask = 0, c_alpha = 0, c_shade = 0;
+    auto shade_queue = [&](int n) {
+        if (lane < n) {
+            const int k = qk[lane];
+            const float wk = qw[lane];
+            float p[3], rgb[3];
+            point(k, p);
+            k4c_shade<WIDTH>(G, p, R.vd, rgb);
+            acc_r = fmaf(wk, rgb[0], acc_r);
+            acc_g = fmaf(wk, rgb[1], acc_g);
+            acc_b = fmaf(wk, rgb[2], acc_b);
+            acc_d = fmaf(wk, (float)k, acc_d);
+        }
+    };
+    for (int base = 0; base < n_steps; base += 64) {
+        if (stopped && !count && filt) break;             // (thres == 0: the samples behind the stop are kept and move the last step)
+        const int k = base + lane;
+        float p[3] = {0.f, 0.f, 0.f};
+        bool pre = false;
+        if (k < n_steps) {
+            point(k, p);
+            pre = BG ? true : !k4s_outbbox(p, G.mn, G.mx);
+        }
+        bool keep = pre;
+        if (keep) keep = k4s_maskcache(G.mask, p[0], p[1], p[2], G.sc, G.sh, G.MX, G.MY, G.MZ) != 0;
+        float alpha = 0.f;
+        if (keep && (!stopped || count)) {
+            size_t idx[8]; float w[8];
+            k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, G.X, G.Y, G.Z, idx, w);
+            float e;
+            k4s_raw2alpha(k4s_grid_blend(G.density, idx, w), A.act_shift, A.interval, e, alpha);
+        }
+        const bool apass = keep && (filt ? alpha > A.thres : true);
+        // transmittance: the exact sequential product of k_alpha2weight over the alpha-passing samples in step order
+        float myw = 0.f;
+        bool wpass = false;
+        uint64_t bm = __ballot(apass);
+        while (bm && !stopped) {
+            const int l = __builtin_ctzll(bm);
+            const float al = k4_readlane(alpha, l);
+            if (lane == l) myw = T * al;
+            T = fmaf(-T, al, T);
+            bm &= bm - 1;
+            if (T < 1e-3f) stopped = true;
+            if (lane == l) wpass = filt ? myw > A.thres : true;
+        }
+        if (count) {
+            c_pre += __popcll(__ballot(pre));
+            c_mask += __popcll(__ballot(keep));
+            c_alpha += __popcll(__ballot(apass));
+        }
+        if (filt ? wpass : keep) my_last = k;
+        const uint64_t sm = __ballot(wpass);
+        const int ns = __popcll(sm);
+        c_shade += ns;
+        if (wpass) {
+            const int slot = nq + __popcll(sm & below);
+            qk[slot] = k;
+            qw[slot] = myw;
+        }
+        nq += ns;
+        __syncthreads();
+        if (nq >= 64) {
+            shade_queue(64);
+            __syncthreads();
+            int rest = nq - 64, mk = 0; float mw = 0.f;
+            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
+            __syncthreads();
+            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
+            __syncthreads();
+            nq = rest;
+        }
+    }
+    shade_queue(nq);
+    __syncthreads();                                       // the next pass refills the queue
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_r += __shfl_down(acc_r, off);
+        acc_g += __shfl_down(acc_g, off);
+        acc_b += __shfl_down(acc_b, off);
+        acc_d += __shfl_down(acc_d, off);
+        my_last = max(my_last, __shfl_xor(my_last, off));
+    }
+    T_out = T;
+    sum[0] = acc_r; sum[1] = acc_g; sum[2] = acc_b; sum[3] = acc_d;
+    last = my_last;
+    if (!filt) c_shade = c_alpha;                          // no weight filter: every alpha sample is shaded (w = 0 behind the stop)
+    cnt[0] = c_pre; cnt[1] = c_mask; cnt[2] = c_alpha; cnt[3] = c_shade;
+}
+
+template <int WF, int WB>
+__global__ __launch_bounds__(64) void k_march_bivox(const K4BivoxArgs A) {
+    __shared__ int qk[128];
+    __shared__ float qw[128];
+    const int64_t ray = blockIdx.x;
+    if (ray >= A.n_rays) return;
+    const int lane = k4_lane();
+    K4BivoxRay R;
+    {
+        const float dx = A.rd[ray * 3 + 0], dy = A.rd[ray * 3 + 1], dz = A.rd[ray * 3 + 2];
+        const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+        const float c[3] = {A.cx, A.cy, A.cz}, r[3] = {A.rx, A.ry, A.rz}, dv[3] = {dx, dy, dz};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            R.o[a] = __fdiv_rn(__fsub_rn(A.ro[ray * 3 + a], c[a]), r[a]);
+            R.d[a] = __fdiv_rn(dv[a], dn);
+            R.vd[a] = A.vd[ray * 3 + a];
+        }
+    }
+    // sample_pts_on_rays of the unit cube, near 0 (k_pts_count / k_pts_fill)
+    float t_min, t_max;
+    aabb_t(R.o, R.d, A.ph[0].mn, A.ph[0].mx, 0.f, A.far, 0, t_min, t_max);
+    const float rn = ray_norm(R.d, 0);
+    int64_t n64 = n_steps_of(t_min, t_max, rn, A.stepdist);
+    const int n_fg = (int)(n64 < 0 ? 0 : (n64 > (1 << 30) ? (1 << 30) : n64));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        R.start[a] = fmaf(R.d[a], t_min, R.o[a]);
+        R.dir[a] = R.d[a] / rn;
+    }
+    R.t_max = t_max;
+    float T_f, T_b = 1.f, sum_f[4], sum_b[4] = {0.f, 0.f, 0.f, 0.f};
+    int last_f, last_b = -1;
+    unsigned long long cnt_f[4], cnt_b[4] = {0, 0, 0, 0};
+    k4b_pass<WF, false>(A, A.ph[0], R, n_fg, lane, qk, qw, T_f, sum_f, last_f, cnt_f);
+    if (T_f > A.thres)                                     // lib/dbvgo.py:258-262 (applied whatever the threshold)
+        k4b_pass<WB, true>(A, A.ph[1], R, A.n_outer, lane, qk, qw, T_b, sum_b, last_b, cnt_b);
+    if (lane == 0) {
+        const float lf = fmaxf(0.f, (float)last_f);        // segment max seeded with 0, then with the foreground's (lib/dbvgo.py:382-391)
+        const float lb = fmaxf(lf, (float)last_b);
+        const float tt = __fmul_rn(T_f, T_b);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            A.rgb[ray * 3 + c] = __fadd_rn(__fadd_rn(sum_f[c], __fmul_rn(T_f, sum_b[c])), __fmul_rn(tt, A.bg));
+        A.depth[ray] = __fadd_rn(__fadd_rn(sum_f[3], __fmul_rn(T_f, __fadd_rn(__fadd_rn(1.f, lf), sum_b[3]))),
+                                 __fmul_rn(tt, __fadd_rn(__fadd_rn(2.f, lf), lb)));
+        A.ainv_fg[ray] = T_f;
+        A.ainv_bg[ray] = T_b;
+        if (A.counters != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                atomicAdd(&A.counters[i], cnt_f[i]);
+                atomicAdd(&A.counters[4 + i], cnt_b[i]);
+            }
+        }
+    }
+}
+
+extern "C" int k4_march_bivox_fwd(const k4_bivox_desc* g, void* stream) {
+    REQ(g && g->n_rays >= 0 && g->n_outer > 0 && g->stepdist > 0.f);
+    if (g->n_rays == 0) return K4_OK;
+    REQ(g->n_rays <= 0x7fffffff);
+    REQ(g->rays_o && g->rays_d && g->viewdirs && g->xyz_min && g->xyz_max && g->rgb && g->depth && g->alphainv_fg && g->alphainv_bg);
+    const int W0 = g->width[0], W1 = g->width[1];
+    if (W0 != 0 && W0 != 32 && W0 != 64 && W0 != 128) return K4_ERR_UNSUPPORTED;
+    if (W1 != 0 && W1 != W0) return K4_ERR_UNSUPPORTED;
+    K4BivoxArgs A;
+    for (int i = 0; i < 2; ++i) {
+        REQ(g->density[i] && g->k0[i] && g->mask[i] && g->xyz2ijk_scale[i] && g->xyz2ijk_shift[i]);
+        REQ(g->dims[i][0] > 0 && g->dims[i][1] > 0 && g->dims[i][2] > 0 && g->mask_dims[i][0] > 0 && g->mask_dims[i][1] > 0 && g->mask_dims[i][2] > 0);
+        const int W = g->width[i];
+        if (W == 0) { REQ(g->k0_ch[i] == 3); }
+        else {
+            if (g->n_hidden[i] != 0 && g->n_hidden[i] != 1) return K4_ERR_UNSUPPORTED;
+            REQ(g->n_pe >= 0 && g->dim0[i] == g->k0_ch[i] + 3 + 6 * g->n_pe && (g->n_pe == 0 || g->viewfreq));
+            REQ(g->w1[i] && g->b1[i] && g->w3[i] && g->b3[i] && (g->n_hidden[i] == 0 || (g->w2[i] && g->b2[i])));
+        }
+        K4ContractedArgs& P = A.ph[i];
+        P = K4ContractedArgs{};
+        P.density = g->density[i]; P.k0 = g->k0[i]; P.C = g->k0_ch[i]; P.X = g->dims[i][0]; P.Y = g->dims[i][1]; P.Z = g->dims[i][2];
+        P.mn = g->xyz_min; P.mx = g->xyz_max;
+        P.mask = g->mask[i]; P.MX = g->mask_dims[i][0]; P.MY = g->mask_dims[i][1]; P.MZ = g->mask_dims[i][2];
+        P.sc = g->xyz2ijk_scale[i]; P.sh = g->xyz2ijk_shift[i];
+        P.w1 = g->w1[i]; P.b1 = g->b1[i]; P.w2 = g->w2[i]; P.b2 = g->b2[i]; P.w3 = g->w3[i]; P.b3 = g->b3[i];
+        P.dim0 = g->dim0[i]; P.n_hidden = g->n_hidden[i]; P.viewfreq = g->viewfreq; P.n_pe = g->n_pe;
+    }
+    A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays;
+    A.cx = g->scene_center[0]; A.cy = g->scene_center[1]; A.cz = g->scene_center[2];
+    A.rx = g->scene_radius[0]; A.ry = g->scene_radius[1]; A.rz = g->scene_radius[2];
+    A.stepdist = g->stepdist; A.far = g->far; A.bg_preserve = g->bg_preserve; A.n_outer = g->n_outer;
+    A.act_shift = g->act_shift; A.interval = g->interval; A.thres = g->fast_color_thres; A.bg = g->bg;
+    A.rgb = g->rgb; A.depth = g->depth; A.ainv_fg = g->alphainv_fg; A.ainv_bg = g->alphainv_bg; A.counters = (unsigned long long*)g->counters;
+    const dim3 grid((unsigned)g->n_rays), block(64);
+#define K4_BIVOX(F, B) hipLaunchKernelGGL((k_march_bivox<F, B>), grid, block, 0, ST, A)
+    switch (W0 * 2 + (W1 != 0)) {
+        case 0:   K4_BIVOX(0, 0); break;
+        case 64:  K4_BIVOX(32, 0); break;
+        case 65:  K4_BIVOX(32, 32); break;
+        case 128: K4_BIVOX(64, 0); break;
+        case 129: K4_BIVOX(64, 64); break;
+        case 256: K4_BIVOX(128, 0); break;
+        default:  K4_BIVOX(128, 128); break;
+    }
+#undef K4_BIVOX
+    return k4_check_launch();
+}
 extern "C" int k4_cumdist_thres(const float* dist, int64_t n_rays, int64_t n_pts, float thres, uint8_t* mask, void* stream) {
     REQ(n_rays >= 0 && n_pts >= 0);
     if (n_rays == 0 || n_pts == 0) return K4_OK;

@@ -31,6 +31,11 @@ _FUSED_WIDTHS = (32, 64, 128)
 _LIVE_MASK = os.environ.get('K4_LIVE_MASK', '1') != '0'      # A/B switch of the density-derived live mask (identical results)
 
 
+def _each(m):
+    """The modules of a ModuleList (DirectBiVoxGO keeps [foreground, background] pairs of grids, masks and rgbnets), else the module itself."""
+    return list(m) if isinstance(m, nn.ModuleList) else [m]
+
+
 class _FusedMarcher:
     """Mixin: device-side descriptors for the fused kernels, cached per parameter version."""
 
@@ -47,10 +52,27 @@ class _FusedMarcher:
         return hit[1]
 
     def _k4_fusable_uncached(self):
+        if isinstance(self.k0, nn.ModuleList):
+            # a pair of grids: each pass shades with its own rgbnet or with sigmoid(k0); the background's width is the foreground's or none
+            nets = _each(self.rgbnet) if self.rgbnet is not None else [None] * len(self.k0)
+            widths = []
+            for net, k0 in zip(nets, self.k0):
+                if net is None:
+                    if k0.channels != 3:
+                        return False
+                    widths.append(0)
+                else:
+                    if not self._k4_net_fusable(net):
+                        return False
+                    widths.append([m for m in net.modules() if isinstance(m, nn.Linear)][0].out_features)
+            return all(w in (0, widths[0]) for w in widths[1:])
         if self.rgbnet is None:
             return self.k0_dim == 3
-        lins = [m for m in self.rgbnet.modules() if isinstance(m, nn.Linear)]
-        acts_ok = all(isinstance(m, (nn.Linear, nn.ReLU, nn.Sequential)) for m in self.rgbnet.modules())
+        return self._k4_net_fusable(self.rgbnet)
+
+    def _k4_net_fusable(self, net):
+        lins = [m for m in net.modules() if isinstance(m, nn.Linear)]
+        acts_ok = all(isinstance(m, (nn.Linear, nn.ReLU, nn.Sequential)) for m in net.modules())
         return (acts_ok and len(lins) in (2, 3) and lins[0].out_features in _FUSED_WIDTHS
                 and lins[-1].out_features == 3 and getattr(self, 'mode_type', 'mlp') not in ('TRANS', 'adain')
                 and not getattr(self, 'rgbnet_full_implicit', False))
@@ -147,16 +169,19 @@ class _FusedMarcher:
         md.n_hidden = len(lins) - 2
         return md, c['mlp_packed']
 
-    def _k4_rgbnet_sigmoid(self, feat, add=None):
+    def _k4_rgbnet_sigmoid(self, feat, add=None, net=None):
         """``torch.sigmoid(self.rgbnet(feat) [+ add])`` of the staged / training forward (lib/dmpigo.py:375-379, lib/dvgo.py:407-412)
         on k4_rgbnet_fwd / k4_rgbnet_bwd (lib/train_ops.py); Linear-ReLU stacks outside those kernels' shapes (deeper, other widths) run
-        layer by layer on the exact-fp32 MFMA 1x1 convolution (inference only).  There is no PyTorch path: anything else raises."""
+        layer by layer on the exact-fp32 MFMA 1x1 convolution (inference only).  There is no PyTorch path: anything else raises.
+        ``net``: one member of a ModuleList of rgbnets (DirectBiVoxGO) instead of ``self.rgbnet``."""
         c = self._k4_cache()
-        if 'rgbnet_native' not in c:
-            c['rgbnet_native'] = train_ops.rgbnet_supported(self.rgbnet)
-        if c['rgbnet_native']:
-            return train_ops.rgbnet_sigmoid(self.rgbnet, feat, add)
-        return train_ops.rgbnet_sigmoid_layers(self.rgbnet, feat, add)
+        slot = 'rgbnet_native' if net is None else ('rgbnet_native', id(net))
+        net = self.rgbnet if net is None else net
+        if slot not in c:
+            c[slot] = train_ops.rgbnet_supported(net)
+        if c[slot]:
+            return train_ops.rgbnet_sigmoid(net, feat, add)
+        return train_ops.rgbnet_sigmoid_layers(net, feat, add)
 
     def _k4_workspace(self, n_rays, img_w, max_steps, device, slot=0):
         """Scratch between the geometry and the shading kernel: worst-case sized (every sample of every ray
@@ -180,7 +205,7 @@ class _FusedMarcher:
 
     def _k4_params_ready(self):
         """A grid whose optimizer step runs on a second stream (MaskedAdam.update_on_side_stream): the current stream waits for it."""
-        for g in (self.density, self.k0):
+        for g in _each(self.density) + _each(self.k0):
             ready = getattr(g, 'params_ready', None)
             if ready is not None:
                 ready()
@@ -226,8 +251,9 @@ class _FusedMarcher:
         Python per frame, which paces bench.py's pipelined loop on a slow host (round 5: 0.86 -> 1.3 ms per frame on some boxes).
         ``build()`` -> (value, tensors to keep alive).  A plan is valid per HIP stream it was built or re-validated on: the first call on
         another stream goes through ``build`` again, which orders that stream behind the load-time kernels (see _k4_live_mask)."""
-        mc = self.mask_cache
-        ts = [self._k4_dense(self.density), self._k4_dense(self.k0), mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
+        ts = []
+        for dens, k0, mc in zip(_each(self.density), _each(self.k0), _each(self.mask_cache)):
+            ts += [self._k4_dense(dens), self._k4_dense(k0), mc.mask, self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift]
         act = getattr(self, 'act_shift', None)
         ts.append(act.grid if isinstance(act, nn.Module) else act)
         if self.rgbnet is not None:

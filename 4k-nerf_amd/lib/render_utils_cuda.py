@@ -82,9 +82,14 @@ def sample_ndc_pts_on_rays(rays_o, rays_d, xyz_min, xyz_max, N_samples):
 
 
 def sample_bg_pts_on_rays(rays_o, rays_d, t_max, bg_preserve, N_samples):
-    raise NotImplementedError(
-        'sample_bg_pts_on_rays serves the unbounded-scene model lib/dbvgo.py only, which no BASELINE '
-        'configuration selects (SURVEY.md 2.2: OUT OF SCOPE)')
+    """-> rays_pts [n_rays, N_samples, 3]: the inverse-sphere background samples of lib/dbvgo.py (render_utils_kernel.cu:301-340)"""
+    n = rays_o.shape[0]
+    pts = torch.empty([n, int(N_samples), 3], dtype=torch.float32, device=rays_o.device)
+    if n == 0:
+        return pts
+    N.check(N.lib().k4_sample_bg_pts_on_rays(N.f32(rays_o), N.f32(rays_d), N.f32(t_max), _f(bg_preserve), int(N_samples), n,
+                                             N.f32(pts), N.stream()), 'sample_bg_pts_on_rays')
+    return pts
 
 
 def maskcache_lookup(world, xyz, xyz2ijk_scale, xyz2ijk_shift):

@@ -30,7 +30,10 @@ def render_frame(model, H, W, K, c2w, ndc, render_kwargs, rays=None):
     out = model(ro, rd, vd, k4_img_w=W, **kw)
     res = {k: out[k].reshape(H, W, -1) for k in ('rgb_marched', 'rgb_feature')}
     res['depth'] = out['depth'].reshape(H, W)
-    res['alphainv_last'] = out['alphainv_last'].reshape(H, W)
+    ainv = out['alphainv_last']
+    if ainv.numel() == 2 * H * W:               # DirectBiVoxGO: cat([fg, bg]); the factor of `bg` in rgb_marched is T_fg * T_bg
+        ainv = ainv[:H * W] * ainv[H * W:]
+    res['alphainv_last'] = ainv.reshape(H, W)
     return res
 
 

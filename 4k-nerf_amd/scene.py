@@ -9,6 +9,7 @@ exercised by both the product modules and the oracle.
   * ``make_llff_checkpoint``  -- DirectMPIGO (NDC) scene, BASELINE configs 2-4
   * ``make_lego_checkpoint``  -- DirectVoxGO bounded scene, BASELINE config 1
   * ``make_unbounded_checkpoint`` / ``unbounded_poses`` -- DirectContractedVoxGO (unbounded_inward) scene and its cameras
+  * ``make_bivox_checkpoint`` -- DirectBiVoxGO (foreground / background grids) scene on the same cameras
   * ``llff_spiral_poses`` / ``lego_pose`` / ``LLFF_K`` -- synthetic cameras
 """
 import math
@@ -292,6 +293,71 @@ def make_unbounded_checkpoint(seed=777, num_voxels=320 ** 3, contracted_norm='in
                      'flip_x': False, 'flip_y': False, 'render_depth': True}
     return {'global_step': 0, 'model_kwargs': kwargs, 'model_state_dict': sd,
             'model_class': 'DirectContractedVoxGO', 'render_kwargs': render_kwargs}
+
+
+def make_bivox_checkpoint(seed=777, num_voxels=160 ** 3, bg_preserve=0.5, bg_use_mlp=True, rgbnet_dim=12, rgbnet_width=128, rgbnet_depth=3,
+                          fast_color_thres=1e-4, viewbase_pe=4, alpha_init=1e-2, stepsize=0.5, n_blobs=10, mask_thres=1e-3):
+    """DirectBiVoxGO checkpoint (lib/dbvgo.py) of an unbounded scene: grid 0 holds density blobs inside the unit cube (the foreground), grid 1 a
+    modulated wall inside the inf-norm shell [bg_preserve, 1] -- the only region of grid 1 the inverse-sphere background sampler reaches.  Both
+    ``mask_cache`` grids come from the 3x3x3 max-pooled alpha (> max(fast_color_thres, mask_thres), so they are not trivial at threshold 0).
+    ``model_kwargs`` are what get_kwargs() stores (xyz_min / xyz_max are the normalised -/+1 box); the scene bbox lives in the ``scene_center`` /
+    ``scene_radius`` buffers.  Cameras: ``unbounded_poses`` / ``unbounded_K``."""
+    g = _gen(seed)
+    center = torch.tensor(UNBOUNDED_CENTER, dtype=torch.float32)
+    radius = torch.full([3], UNBOUNDED_RADIUS, dtype=torch.float32)
+    xyz_min = torch.Tensor([-1, -1, -1])                                # lib/dbvgo.py:36-37
+    xyz_max = torch.Tensor([1, 1, 1])
+    # DirectBiVoxGO._set_grid_resolution (lib/dbvgo.py:130-135), num_voxels_base = num_voxels
+    voxel_size = ((xyz_max - xyz_min).prod() / num_voxels).pow(1 / 3)
+    world_size = ((xyz_max - xyz_min) / voxel_size).long()
+    ws = world_size.tolist()
+    act_shift = torch.FloatTensor([np.log(1 / (1 - alpha_init) - 1)])
+    ax = [_axis(xyz_min[i], xyz_max[i], ws[i]) for i in range(3)]
+    X, Y, Z = torch.meshgrid(*ax, indexing='ij')
+    # foreground: Gaussian blobs with centres in |x| <= 0.6
+    field = torch.zeros(ws)
+    for _ in range(n_blobs):
+        c = [float((torch.rand([], generator=g) * 2 - 1) * 0.6) for _ in range(3)]
+        sg = [float(0.07 + 0.1 * torch.rand([], generator=g)) for _ in range(3)]
+        a = float(22.0 * (0.75 + 0.5 * torch.rand([], generator=g)))
+        field += a * torch.exp(-0.5 * (((X - c[0]) / sg[0]) ** 2 + ((Y - c[1]) / sg[1]) ** 2 + ((Z - c[2]) / sg[2]) ** 2))
+    density_fg = (field - 8.0)[None, None].contiguous()
+    # background: a wall in the middle of the shell, modulated around the sphere (a few opaque patches and gaps)
+    nrm = torch.maximum(torch.maximum(X.abs(), Y.abs()), Z.abs())
+    mid, wid = 0.5 * (1 + bg_preserve), 0.15 * (1 - bg_preserve)
+    shell = torch.exp(-0.5 * ((nrm - mid) / wid) ** 2)
+    ph = [float(torch.rand([], generator=g) * 6.28) for _ in range(3)]
+    mod = 0.5 + 0.5 * torch.sin(3.0 * X + ph[0]) * torch.sin(2.0 * Y + ph[1]) * torch.cos(2.5 * Z + ph[2])
+    density_bg = (24.0 * shell * mod - 8.0)[None, None].contiguous()
+    k0_dims = [rgbnet_dim if rgbnet_dim > 0 else 3, rgbnet_dim if (rgbnet_dim > 0 and bg_use_mlp) else 3]
+    sd = {'scene_center': center.clone(), 'scene_radius': radius.clone(), 'xyz_min': xyz_min.clone(), 'xyz_max': xyz_max.clone(),
+          'act_shift': act_shift}
+    scale = (torch.tensor(ws, dtype=torch.float32) - 1) / (xyz_max - xyz_min)
+    for i, density in enumerate((density_fg, density_bg)):
+        alpha = _raw2alpha(density, act_shift, 1.0)
+        mask = F.max_pool3d(alpha, kernel_size=3, padding=1, stride=1)[0, 0] > max(fast_color_thres, mask_thres)
+        k0 = _smooth3(torch.randn([1, k0_dims[i]] + ws, generator=g) * 0.5).contiguous()
+        sd.update({f'density.{i}.grid': density, f'density.{i}.xyz_min': xyz_min.clone(), f'density.{i}.xyz_max': xyz_max.clone(),
+                   f'k0.{i}.grid': k0, f'k0.{i}.xyz_min': xyz_min.clone(), f'k0.{i}.xyz_max': xyz_max.clone(),
+                   f'mask_cache.{i}.mask': mask, f'mask_cache.{i}.xyz2ijk_scale': scale.clone(),
+                   f'mask_cache.{i}.xyz2ijk_shift': -xyz_min * scale})
+    if rgbnet_dim > 0:
+        sd['viewfreq'] = torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)])
+        for i in range(2 if bg_use_mlp else 1):
+            net = _rgbnet_state(g, 3 + 3 * viewbase_pe * 2 + rgbnet_dim, rgbnet_width, rgbnet_depth, gain=1.5)   # lib/dbvgo.py:94-106
+            sd.update({f'rgbnet.{i}.' + k[len('rgbnet.'):]: v for k, v in net.items()})
+    kwargs = {
+        'xyz_min': xyz_min.numpy().copy(), 'xyz_max': xyz_max.numpy().copy(),
+        'num_voxels': num_voxels, 'num_voxels_base': num_voxels, 'alpha_init': alpha_init,
+        'voxel_size_ratio': 1.0, 'mask_cache_world_size': ws, 'fast_color_thres': fast_color_thres,
+        'bg_preserve': bg_preserve, 'bg_use_mlp': bg_use_mlp,
+        'density_type': 'DenseGrid', 'k0_type': 'DenseGrid', 'density_config': {}, 'k0_config': {},
+        'rgbnet_dim': rgbnet_dim, 'rgbnet_depth': rgbnet_depth, 'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe,
+    }
+    render_kwargs = {'near': 0., 'far': 1e9, 'bg': 1, 'stepsize': stepsize, 'inverse_y': False,
+                     'flip_x': False, 'flip_y': False, 'render_depth': True}
+    return {'global_step': 0, 'model_kwargs': kwargs, 'model_state_dict': sd,
+            'model_class': 'DirectBiVoxGO', 'render_kwargs': render_kwargs}
 
 
 def unbounded_poses(n_frames=8, dist=0.8, height=0.15):

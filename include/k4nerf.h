@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      20      /* 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      21      /* 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -322,6 +322,40 @@ typedef struct k4_contracted_desc {
     float* rgb; float* depth; float* alphainv_last; uint64_t* counters;
 } k4_contracted_desc;
 int k4_march_contracted_fwd(const k4_contracted_desc* desc, void* stream);
+/* ABI 21 -- render_utils_cuda.sample_bg_pts_on_rays (lib/cuda/render_utils_kernel.cu:301-340): the inverse-sphere background samples of DirectBiVoxGO.
+ * rays_o / rays_d [n_rays][3] (normalised scene coordinates, unit directions), t_max [n_rays] (the far slab distance of the unit cube),
+ * out_pts [n_rays][n_samples][3].  Per (ray, step): t = t_max - 1. + 1. / (1. - (float)step / n_samples) with the source's fp64 intermediates
+ * rounded once to fp32; q = o + d t (FMA); |q| = sqrt(fma(z, z, fma(y, y, x x))); R = |q| / max|q_i|;
+ * scale = R R / (|q| |q|) (1. - bg_preserve) + R / |q| bg_preserve (the first product and the sum in fp64, as the literals of the source make them);
+ * p = q scale. */
+int k4_sample_bg_pts_on_rays(const float* rays_o, const float* rays_d, const float* t_max, float bg_preserve, int32_t n_samples, int64_t n_rays,
+                             float* out_pts, void* stream);
+/* ABI 21 -- DirectBiVoxGO inference in ONE launch (lib/dbvgo.py:310-397 under torch.no_grad).  One wave per ray, lanes = 64 consecutive steps in depth
+ * order.  Foreground (grid 0): o' = (o - centre) / radius, d' = d / |d|, the ray-AABB slab of the unit cube with near 0 and `far`, the step count of
+ * infer_n_samples, p = start + dir (stepdist k), bbox test, mask_cache[0], density[0], raw2alpha, alpha > thres, the exact sequential transmittance
+ * product with the T < 1e-3 stop, w > thres; survivors are shaded 64 at a time with k0[0] and rgbnet[0].  Background (grid 1), only when
+ * T_fg > thres: n_outer steps of k4_sample_bg_pts_on_rays from t_max, mask_cache[1], density[1], the same filters and product, k0[1] and rgbnet[1]
+ * (width[1] == 0: sigmoid(k0[1]), k0_ch[1] == 3).  thres == 0 skips both `>` filters (every in-mask sample is kept), as lib/dbvgo.py:273,283 do.
+ *   rgb   = rgb_fg + T_fg rgb_bg + T_fg T_bg bg
+ *   depth = depth_fg + T_fg (1 + last_fg + depth_bg) + T_fg T_bg (2 + last_fg + last_bg),  depth_x = sum w step,
+ *           last_fg = max(0, last kept foreground step), last_bg = max(last_fg, last kept background step)   (lib/dbvgo.py:382-394)
+ * width[0] in {0, 32, 64, 128}, width[1] in {width[0], 0}, n_hidden 0 | 1; anything else returns K4_ERR_UNSUPPORTED (use the staged ops).  Grids
+ * channel-major as stored, rgbnet weights as the nn.Linear tensors (see k4_contracted_desc).  counters: NULL or uint64[8] (ADDED to) =
+ * {in-bbox samples, mask-pass, alpha-pass, shaded} of the foreground, then {samples of the rays that reach the background, mask-pass, alpha-pass,
+ * shaded}.  Nothing per sample goes to memory; no workspace. */
+typedef struct k4_bivox_desc {
+    const float* rays_o; const float* rays_d; const float* viewdirs; int64_t n_rays;
+    float scene_center[3]; float scene_radius[3];
+    float stepdist; float far; float bg_preserve; int32_t n_outer;
+    float act_shift; float interval; float fast_color_thres; float bg;
+    const float* xyz_min; const float* xyz_max;                                  /* device [3] each: the normalised box shared by both grids */
+    const float* density[2]; const float* k0[2]; int32_t k0_ch[2]; int32_t dims[2][3];
+    const uint8_t* mask[2]; int32_t mask_dims[2][3]; const float* xyz2ijk_scale[2]; const float* xyz2ijk_shift[2];
+    const float* w1[2]; const float* b1[2]; const float* w2[2]; const float* b2[2]; const float* w3[2]; const float* b3[2];
+    int32_t dim0[2]; int32_t width[2]; int32_t n_hidden[2]; const float* viewfreq; int32_t n_pe;
+    float* rgb; float* depth; float* alphainv_fg; float* alphainv_bg; uint64_t* counters;
+} k4_bivox_desc;
+int k4_march_bivox_fwd(const k4_bivox_desc* desc, void* stream);
 /* The interior of a decoded window into the frame (SFTNet.tile_process, lib/sr_esrnet.py:508-524: output_tile[..., crop] -> output[..., tile]) in ONE pass:
  * dst[c * dst_plane_stride + y * dst_row_stride + x] = src[((oy + y) * src_w + ox + x) * channels + c], 0 <= y < th, 0 <= x < tw, c < channels (<= 4);
  * src: the window's NHWC result [*][src_w][channels], dst: planes of the [1, 3, 4H, 4W] frame (pre-offset to the tile) or of a gather buffer. */
