@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 21
+K4_ABI_VERSION = 22
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -52,6 +52,18 @@ class BivoxDesc(C.Structure):          # k4_bivox_desc (ABI 21)
                 ('w1', C.c_void_p * 2), ('b1', C.c_void_p * 2), ('w2', C.c_void_p * 2), ('b2', C.c_void_p * 2), ('w3', C.c_void_p * 2), ('b3', C.c_void_p * 2),
                 ('dim0', C.c_int32 * 2), ('width', C.c_int32 * 2), ('n_hidden', C.c_int32 * 2), ('viewfreq', C.c_void_p), ('n_pe', C.c_int32),
                 ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_fg', C.c_void_p), ('alphainv_bg', C.c_void_p), ('counters', C.c_void_p)]
+
+
+class VqDesc(C.Structure):             # k4_vq_desc (ABI 22)
+    _fields_ = [('rays_o', C.c_void_p), ('rays_d', C.c_void_p), ('viewdirs', C.c_void_p), ('n_rays', C.c_int64), ('n_samples', C.c_int32),
+                ('density', C.c_void_p), ('dims', C.c_int32 * 3), ('act_shift', C.c_void_p), ('act_depth', C.c_int32), ('xyz_min', C.c_void_p), ('xyz_max', C.c_void_p),
+                ('mask', C.c_void_p), ('mask_dims', C.c_int32 * 3), ('xyz2ijk_scale', C.c_void_p), ('xyz2ijk_shift', C.c_void_p),
+                ('interval', C.c_float), ('fast_color_thres', C.c_float), ('bg', C.c_float),
+                ('posfreq', C.c_void_p), ('n_pe', C.c_int32),
+                ('pw1', C.c_void_p), ('pb1', C.c_void_p), ('pw2', C.c_void_p), ('pb2', C.c_void_p), ('dim', C.c_int32), ('codebook', C.c_void_p), ('n_embed', C.c_int32),
+                ('w1', C.c_void_p), ('b1', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p), ('w3', C.c_void_p), ('b3', C.c_void_p),
+                ('dim0', C.c_int32), ('width', C.c_int32), ('n_hidden', C.c_int32),
+                ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_last', C.c_void_p)]
 
 
 class MlpDesc(C.Structure):
@@ -277,6 +289,18 @@ _EXTRA_SIGS = {
     'k4_tensorf_sample_backward': ([_P] * 8 + [_I32] * 6 + [_P, _P, _P, _I64] + [_P] * 8, C.c_int),
     'k4_tensorf_dense': ([_P] * 7 + [_I32] * 6 + [_P, _P], C.c_int),
     'k4_tensorf_tv_add_grad': ([_P, _P, _I32, _I32, _I32, _F, _F, _P], C.c_int),
+    'k4_vq_project_fwd': ([_P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    'k4_vq_project_bwd_workspace_bytes': ([_I64, _I32, _I32], C.c_int64),
+    'k4_vq_project_bwd': ([_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P], C.c_int),
+    'k4_vq_codebook_floats': ([_I32, _I32], C.c_int64),
+    'k4_vq_chunk_codes': ([_I32], C.c_int32),
+    'k4_vq_prepare_codebook': ([_P, _I32, _I32, _P, _P], C.c_int),
+    'k4_vq_assign_workspace_bytes': ([_I64, _I32, _I32, _I32], C.c_int64),
+    'k4_vq_assign': ([_P, _I64, _I32, _P, _I32, _P, _P, _P, _I32, _P, _I64, _P], C.c_int),
+    'k4_vq_update_codebook': ([_P, _I64, _I32, _I32, _F, _F, _F, _F, _P, _P, _P, _P], C.c_int),
+    'k4_grid_sample_3d_backward_terms': ([_P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P], C.c_int),
+    'k4_sorted_segment_add': ([_P, _P, _I64, _I64, _P, _P], C.c_int),
+    'k4_march_vq_fwd': ([C.POINTER(VqDesc), _P], C.c_int),
     'k4_frame_metrics': ([_P, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(C.c_double), _I32, C.c_double, C.c_double, _P, _P, _P, _P], C.c_int),
 }
 

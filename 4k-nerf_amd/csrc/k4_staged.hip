@@ -5,6 +5,7 @@
 // the fused kernels of k4_march.hip, which share the arithmetic written here op for op.
 // All are HBM-streaming, one thread per element (or one WAVE per ray for the transmittance scan).
 #include "k4_common.h"
+#include "k4_vq.h"
 
 #define K4_THREADS 256
 static inline unsigned k4_blocks(int64_t n) { return (unsigned)((n + K4_THREADS - 1) / K4_THREADS); }
@@ -970,6 +971,46 @@ extern "C" int k4_grid_sample_3d_backward(const float* grad_out, int32_t C, int3
     hipLaunchKernelGGL(k_grid_sample_bwd, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, grad_out, C, X, Y, Z, xyz, mn, mx, n, grad_grid);
     return k4_check_launch();
 }
+// The one-channel gradient in a FIXED summation order (a model whose training step must repeat bit for bit: lib/dvqgo.py).  k_gsb_terms writes a
+// sample's eight (voxel, weight * grad_out) terms, voxel -1 where the weight is 0; the host sorts them by voxel with a stable sort (sample order kept
+// inside a voxel); k_sorted_segment_add gives every run of equal voxels to the thread at its head, which adds the run in order.
+__global__ void k_gsb_terms(const float* __restrict__ gout, int X, int Y, int Z, const float* __restrict__ xyz, const float* __restrict__ mn,
+                            const float* __restrict__ mx, int64_t n, int64_t* __restrict__ vox, float* __restrict__ val) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    size_t idx[8]; float w[8];
+    k4s_grid_corners(xyz[i * 3 + 0], xyz[i * 3 + 1], xyz[i * 3 + 2], mn, mx, X, Y, Z, idx, w);
+    const float g = gout[i];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        vox[i * 8 + c] = w[c] != 0.f ? (int64_t)idx[c] : -1;
+        val[i * 8 + c] = g * w[c];
+    }
+}
+__global__ void k_sorted_segment_add(const int64_t* __restrict__ key, const float* __restrict__ val, int64_t m, int64_t n_out, float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const int64_t k = key[t];
+    if (k < 0 || k >= n_out || (t > 0 && key[t - 1] == k)) return;
+    float acc = 0.f;
+    for (int64_t j = t; j < m && key[j] == k; ++j) acc += val[j];
+    out[k] += acc;
+}
+extern "C" int k4_grid_sample_3d_backward_terms(const float* grad_out, int32_t X, int32_t Y, int32_t Z, const float* xyz, const float* mn, const float* mx,
+                                                int64_t n, int64_t* voxel, float* term, void* stream) {
+    REQ(X > 0 && Y > 0 && Z > 0 && mn && mx && n >= 0);
+    if (n == 0) return K4_OK;
+    REQ(xyz && grad_out && voxel && term);
+    hipLaunchKernelGGL(k_gsb_terms, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, grad_out, X, Y, Z, xyz, mn, mx, n, voxel, term);
+    return k4_check_launch();
+}
+extern "C" int k4_sorted_segment_add(const int64_t* key, const float* val, int64_t m, int64_t n_out, float* out, void* stream) {
+    REQ(m >= 0 && n_out > 0 && out);
+    if (m == 0) return K4_OK;
+    REQ(key && val);
+    hipLaunchKernelGGL(k_sorted_segment_add, dim3(k4_blocks(m)), dim3(K4_THREADS), 0, ST, key, val, m, n_out, out);
+    return k4_check_launch();
+}
 extern "C" int64_t k4_grid_sample_3d_backward_workspace_bytes(int32_t C, int32_t X, int32_t Y, int32_t Z) {
     if (C <= 1 || C > 32 || X <= 0 || Y <= 0 || Z <= 0) return -1;          // one channel: the layouts coincide, use k4_grid_sample_3d_backward
     const int64_t nvox = (int64_t)X * Y * Z;
@@ -1087,56 +1128,62 @@ __device__ __forceinline__ void k4c_point(const K4ContractedArgs& A, const float
     }
 }
 
+// The Linear-ReLU rgbnet of a shaded sample as fp32 FMA chains + sigmoid, shared by the one-launch marchers.  The first layer's inputs come in order:
+// `pre(h)` adds the leading i0 inputs a caller holds in registers (none: a no-op), in(i) yields input i for i0 <= i < nin.
+template <int WIDTH, class PRE, class IN>
+__device__ __forceinline__ void k4c_mlp(const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                        const float* __restrict__ w3, const float* __restrict__ b3, int dim0, int n_hidden, int i0, int nin,
+                                        PRE&& pre, IN&& in, float (&rgb)[3]) {
+    float h[WIDTH];
+#pragma unroll
+    for (int j = 0; j < WIDTH; ++j) h[j] = b1[j];
+    pre(h);
+    for (int i = i0; i < nin; ++i) {
+        const float x = in(i);
+#pragma unroll
+        for (int j = 0; j < WIDTH; ++j) h[j] = fmaf(w1[(size_t)j * dim0 + i], x, h[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < WIDTH; ++j) h[j] = fmaxf(h[j], 0.f);
+    float out[3] = {b3[0], b3[1], b3[2]};
+    if (n_hidden == 0) {
+#pragma unroll
+        for (int j = 0; j < WIDTH; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = fmaf(w3[c * WIDTH + j], h[j], out[c]);
+    } else {
+        for (int j2 = 0; j2 < WIDTH; ++j2) {
+            float acc = b2[j2];
+#pragma unroll
+            for (int i = 0; i < WIDTH; ++i) acc = fmaf(w2[(size_t)j2 * WIDTH + i], h[i], acc);
+            acc = fmaxf(acc, 0.f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = fmaf(w3[c * WIDTH + j2], acc, out[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-out[c]));
+}
+
 template <int WIDTH>
 __device__ __forceinline__ void k4c_shade(const K4ContractedArgs& A, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
     size_t idx[8]; float w[8];
     k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
     const size_t plane = (size_t)A.X * A.Y * A.Z;
-    if (WIDTH == 0) {
+    if constexpr (WIDTH == 0) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-k4s_grid_blend(A.k0 + plane * c, idx, w)));
-        return;
-    }
-    float h[WIDTH > 0 ? WIDTH : 1];
-#pragma unroll
-    for (int j = 0; j < WIDTH; ++j) h[j] = A.b1[j];
-    const int P = A.n_pe;
-    const int nin = A.C + 3 + 6 * P;
-    for (int i = 0; i < nin; ++i) {
-        float x;
-        if (i < A.C) x = k4s_grid_blend(A.k0 + plane * i, idx, w);
-        else {
-            const int e = i - A.C;
-            if (e < 3) x = vd[e];
-            else {
-                const int q = e - 3, sc = q / (3 * P), r = q - sc * 3 * P, dd = r / P, f = r - dd * P;
-                const float v = __fmul_rn(vd[dd], A.viewfreq[f]);
-                x = sc == 0 ? sinf(v) : cosf(v);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WIDTH; ++j) h[j] = fmaf(A.w1[(size_t)j * A.dim0 + i], x, h[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < WIDTH; ++j) h[j] = fmaxf(h[j], 0.f);
-    float out[3] = {A.b3[0], A.b3[1], A.b3[2]};
-    if (A.n_hidden == 0) {
-#pragma unroll
-        for (int j = 0; j < WIDTH; ++j)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[c] = fmaf(A.w3[c * WIDTH + j], h[j], out[c]);
     } else {
-        for (int j2 = 0; j2 < WIDTH; ++j2) {
-            float acc = A.b2[j2];
-#pragma unroll
-            for (int i = 0; i < WIDTH; ++i) acc = fmaf(A.w2[(size_t)j2 * WIDTH + i], h[i], acc);
-            acc = fmaxf(acc, 0.f);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[c] = fmaf(A.w3[c * WIDTH + j2], acc, out[c]);
-        }
+        const int P = A.n_pe;
+        k4c_mlp<WIDTH>(A.w1, A.b1, A.w2, A.b2, A.w3, A.b3, A.dim0, A.n_hidden, 0, A.C + 3 + 6 * P, [](float (&)[WIDTH]) {}, [&](int i) -> float {
+            if (i < A.C) return k4s_grid_blend(A.k0 + plane * i, idx, w);
+            const int e = i - A.C;
+            if (e < 3) return vd[e];
+            const int q = e - 3, sc = q / (3 * P), r = q - sc * 3 * P, dd = r / P, f = r - dd * P;
+            const float v = __fmul_rn(vd[dd], A.viewfreq[f]);
+            return sc == 0 ? sinf(v) : cosf(v);
+        }, rgb);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-out[c]));
 }
 
 template <int WIDTH>
@@ -1313,6 +1360,194 @@ extern "C" int k4_march_contracted_fwd(const k4_contracted_desc* g, void* stream
         case 64:  hipLaunchKernelGGL(k_march_contracted<64>, grid, block, 0, ST, A); break;
         default:  hipLaunchKernelGGL(k_march_contracted<128>, grid, block, 0, ST, A); break;
     }
+    return k4_check_launch();
+}
+// ---------------------------------------------------------------- DirectQVGO inference: ONE launch per call (k4_march_vq_fwd)
+// DirectMPIGO's geometry with a codebook colour feature (lib/dvqgo.py:279-408 under torch.no_grad, module in eval mode).  One wave walks one ray, lanes = 64
+// consecutive samples, in depth order, as k_march_contracted does:
+//   geometry  the three filters of k_train_select_mpi, expression for expression (NDC point, bounding box, mask cache, density + act_shift grid,
+//             raw2alpha with shift 0, alpha > thres, the sequential transmittance product with the T < 1e-3 stop, weight > thres)
+//   shading   survivors are queued in LDS (step, w) and shaded 64 at a time, lane = survivor: the positional embedding (k_rgbnet_input_mpi's
+//             arithmetic), the two-layer projection, the codeword search over the prepared codebook and v + (e - v) (k4_vq.h: the expressions of the
+//             staged lookup, so the chosen codeword is its choice), the rgbnet on [vq_emb | pe_emb | viewdirs] (k4c_mlp), sigmoid;
+//             sum w rgb, sum w (step + 0.5) / n_samples (depth), alphainv_last = T, rgb += T bg.  Nothing per sample is written to memory.
+struct K4VqArgs {
+    const float *ro, *rd, *vd; int64_t n_rays; int n_samples;
+    const float* density; int X, Y, Z; const float* act; int AD; const float *mn, *mx;
+    const uint8_t* mask; int MX, MY, MZ; const float *sc, *sh;
+    float interval, thres, bg;
+    const float* posfreq; int n_pe;
+    const float *pw1, *pb1, *pw2, *pb2; int dim; const float* codebook; int n_embed;
+    const float *w1, *b1, *w2, *b2, *w3, *b3; int dim0, n_hidden;
+    float *rgb, *depth, *ainv;
+};
+
+template <int WIDTH, int MAXD>
+__device__ __forceinline__ void k4v_shade(const K4VqArgs& A, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
+    const int P = A.n_pe, npe = 3 + 6 * P;
+    float spa[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {                                                           // pe_spa, lib/dvqgo.py:322: sub, div, flip, mul, sub
+        const int a = 2 - j;
+        spa[j] = __fsub_rn(__fmul_rn(__fdiv_rn(__fsub_rn(p[a], A.mn[a]), __fsub_rn(A.mx[a], A.mn[a])), 2.f), 1.f);
+    }
+    auto pe = [&](int col) -> float {                                                       // pe_emb column (k_rgbnet_input_mpi)
+        if (col < 3) return col == 0 ? spa[0] : col == 1 ? spa[1] : spa[2];
+        const int c2 = col - 3, which = c2 / (3 * P), r = c2 - which * 3 * P, d = r / P, f = r - d * P;
+        const float arg = __fmul_rn(d == 0 ? spa[0] : d == 1 ? spa[1] : spa[2], A.posfreq[f]);
+        return which == 0 ? sinf(arg) : cosf(arg);
+    };
+    float h[MAXD], v[MAXD];
+    vq_project_point<MAXD>(pe, npe, A.dim, k4_const(A.pw1), k4_const(A.pb1), k4_const(A.pw2), k4_const(A.pb2), h, v);
+    const int S = (A.dim + 1 + 3) / 4 * 4;
+    float best = 0.f;
+    int best_e = -1;
+    vq_scan_rows<MAXD>(k4_const(A.codebook), A.n_embed, 0, S, A.dim, v, vq_norm2(v, A.dim), best, best_e);
+    const float* const row = A.codebook + (size_t)best_e * S;
+#pragma unroll
+    for (int j = 0; j < MAXD; ++j)
+        if (j < A.dim) v[j] = __fadd_rn(v[j], __fsub_rn(row[j], v[j]));                      // vq_input + (quantize - vq_input), lib/grid.py:96
+    k4c_mlp<WIDTH>(A.w1, A.b1, A.w2, A.b2, A.w3, A.b3, A.dim0, A.n_hidden, A.dim, A.dim + npe + 3, [&](float (&hh)[WIDTH]) {
+#pragma unroll
+        for (int c = 0; c < MAXD; ++c)
+            if (c < A.dim) {
+#pragma unroll
+                for (int j = 0; j < WIDTH; ++j) hh[j] = fmaf(A.w1[(size_t)j * A.dim0 + c], v[c], hh[j]);
+            }
+    }, [&](int i) -> float {
+        const int e = i - A.dim;
+        if (e < npe) return pe(e);
+        return e == npe ? vd[0] : e == npe + 1 ? vd[1] : vd[2];
+    }, rgb);
+}
+
+template <int WIDTH, int MAXD>
+__global__ __launch_bounds__(64) void k_march_vq(const K4VqArgs A) {
+    __shared__ int qk[128];
+    __shared__ float qw[128];
+    const int64_t ray = blockIdx.x;
+    if (ray >= A.n_rays) return;
+    const int lane = k4_lane();
+    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const float vd[3] = {A.vd[ray * 3 + 0], A.vd[ray * 3 + 1], A.vd[ray * 3 + 2]};
+    float T = 1.f;
+    bool stopped = false;
+    int nq = 0;
+    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
+    auto shade_queue = [&](int n) {
+        if (lane < n) {
+            const int k = qk[lane];
+            const float wk = qw[lane];
+            float p[3], rgb[3];
+            k4s_ndc_point(A.ro, A.rd, ray, k, A.n_samples, p);
+            k4v_shade<WIDTH, MAXD>(A, p, vd, rgb);
+            acc_r = fmaf(wk, rgb[0], acc_r);
+            acc_g = fmaf(wk, rgb[1], acc_g);
+            acc_b = fmaf(wk, rgb[2], acc_b);
+            acc_d = fmaf(wk, __fdiv_rn((float)k + 0.5f, (float)A.n_samples), acc_d);
+        }
+    };
+    for (int base = 0; base < A.n_samples && !stopped; base += 64) {
+        const int k = base + lane;
+        const bool valid = k < A.n_samples;
+        float p[3];
+        k4s_ndc_point(A.ro, A.rd, ray, valid ? k : 0, A.n_samples, p);
+        bool f2 = valid && !k4s_outbbox(p, A.mn, A.mx);
+        if (f2) f2 = k4s_maskcache(A.mask, p[0], p[1], p[2], A.sc, A.sh, A.MX, A.MY, A.MZ) != 0;
+        float alpha = 0.f;
+        if (f2) {
+            size_t idx[8]; float w[8];
+            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
+            const float den = k4s_grid_blend(A.density, idx, w);
+            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, 1, 1, A.AD, idx, w);
+            const float ash = k4s_grid_blend(A.act, idx, w);
+            const float sum = den + ash;
+            float e;
+            k4s_raw2alpha(sum, 0.f, A.interval, e, alpha);
+            f2 = A.thres > 0.f ? alpha > A.thres : true;
+        }
+        float myw = 0.f;
+        bool hit = false;                                         // this lane's sample entered the transmittance product
+        uint64_t bm = __ballot(f2);
+        while (bm && !stopped) {
+            const int l = __builtin_ctzll(bm);
+            const float al = k4_readlane(alpha, l);
+            if (lane == l) { myw = T * al; hit = true; }
+            T = fmaf(-T, al, T);
+            bm &= bm - 1;
+            if (T < 1e-3f) stopped = true;
+        }
+        // weight > thres; without a threshold every alpha sample is shaded, those behind the stop with weight 0 (they add nothing: not queued)
+        const bool wpass = A.thres > 0.f ? (f2 && myw > A.thres) : hit;
+        const uint64_t sm = __ballot(wpass);
+        const int ns = __popcll(sm);
+        if (wpass) {
+            const int slot = nq + __popcll(sm & below);
+            qk[slot] = k;
+            qw[slot] = myw;
+        }
+        nq += ns;
+        __syncthreads();
+        if (nq >= 64) {
+            shade_queue(64);
+            __syncthreads();
+            int rest = nq - 64, mk = 0; float mw = 0.f;
+            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
+            __syncthreads();
+            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
+            __syncthreads();
+            nq = rest;
+        }
+    }
+    shade_queue(nq);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        acc_r += __shfl_down(acc_r, off);
+        acc_g += __shfl_down(acc_g, off);
+        acc_b += __shfl_down(acc_b, off);
+        acc_d += __shfl_down(acc_d, off);
+    }
+    if (lane == 0) {
+        A.rgb[ray * 3 + 0] = fmaf(T, A.bg, acc_r);
+        A.rgb[ray * 3 + 1] = fmaf(T, A.bg, acc_g);
+        A.rgb[ray * 3 + 2] = fmaf(T, A.bg, acc_b);
+        A.depth[ray] = acc_d;
+        A.ainv[ray] = T;
+    }
+}
+
+extern "C" int k4_march_vq_fwd(const k4_vq_desc* g, void* stream) {
+    REQ(g && g->n_rays >= 0 && g->n_samples > 1);
+    if (g->n_rays == 0) return K4_OK;
+    REQ(g->rays_o && g->rays_d && g->viewdirs && g->density && g->act_shift && g->mask && g->xyz_min && g->xyz_max && g->xyz2ijk_scale && g->xyz2ijk_shift);
+    REQ(g->rgb && g->depth && g->alphainv_last);
+    REQ(g->dims[0] > 0 && g->dims[1] > 0 && g->dims[2] > 0 && g->act_depth > 0 && g->mask_dims[0] > 0 && g->mask_dims[1] > 0 && g->mask_dims[2] > 0);
+    REQ(g->n_pe >= 0 && g->n_pe <= 10 && (g->n_pe == 0 || g->posfreq) && g->dim >= 1 && g->dim <= VQ_MAXD && g->n_embed >= 1 && g->codebook);
+    REQ(g->pw1 && g->pb1 && g->pw2 && g->pb2 && g->w1 && g->b1 && g->w3 && g->b3);
+    REQ((g->n_hidden == 0 || g->n_hidden == 1) && (g->n_hidden == 0 || (g->w2 && g->b2)) && g->dim0 == g->dim + 3 + 6 * g->n_pe + 3);
+    if (g->n_rays > 0x7fffffffLL) return K4_ERR_UNSUPPORTED;
+    const int W = g->width;
+    if (W != 32 && W != 64 && W != 128) return K4_ERR_UNSUPPORTED;
+    K4VqArgs A;
+    A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays; A.n_samples = g->n_samples;
+    A.density = g->density; A.X = g->dims[0]; A.Y = g->dims[1]; A.Z = g->dims[2]; A.act = g->act_shift; A.AD = g->act_depth; A.mn = g->xyz_min; A.mx = g->xyz_max;
+    A.mask = g->mask; A.MX = g->mask_dims[0]; A.MY = g->mask_dims[1]; A.MZ = g->mask_dims[2]; A.sc = g->xyz2ijk_scale; A.sh = g->xyz2ijk_shift;
+    A.interval = g->interval; A.thres = g->fast_color_thres; A.bg = g->bg;
+    A.posfreq = g->posfreq; A.n_pe = g->n_pe;
+    A.pw1 = g->pw1; A.pb1 = g->pb1; A.pw2 = g->pw2; A.pb2 = g->pb2; A.dim = g->dim; A.codebook = g->codebook; A.n_embed = g->n_embed;
+    A.w1 = g->w1; A.b1 = g->b1; A.w2 = g->w2; A.b2 = g->b2; A.w3 = g->w3; A.b3 = g->b3; A.dim0 = g->dim0; A.n_hidden = g->n_hidden;
+    A.rgb = g->rgb; A.depth = g->depth; A.ainv = g->alphainv_last;
+    const dim3 grid((unsigned)g->n_rays), block(64);
+    // register arrays sized for the codeword's channel count: 8 | 16 | 32 (the same guarded chains: the same bits)
+#define K4_VQ(WD) do { if (g->dim <= 8) hipLaunchKernelGGL((k_march_vq<WD, 8>), grid, block, 0, ST, A); \
+                       else if (g->dim <= 16) hipLaunchKernelGGL((k_march_vq<WD, 16>), grid, block, 0, ST, A); \
+                       else hipLaunchKernelGGL((k_march_vq<WD, 32>), grid, block, 0, ST, A); } while (0)
+    switch (W) {
+        case 32:  K4_VQ(32); break;
+        case 64:  K4_VQ(64); break;
+        default:  K4_VQ(128); break;
+    }
+#undef K4_VQ
     return k4_check_launch();
 }
 // ---------------------------------------------------------------- sample_bg_pts_on_rays (.cu:301-340): DirectBiVoxGO's inverse-sphere background samples

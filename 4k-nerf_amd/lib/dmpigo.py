@@ -71,7 +71,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         self.dim_rend = 3
         self.act_type, self.mode_type = kwargs.get('act_type', 'relu'), kwargs.get('mode_type', 'mlp')
         self.k0_dim = rgbnet_dim if rgbnet_dim > 0 else 3
-        self.k0 = self._new_grid(k0_type, self.k0_dim, k0_config)
+        self.k0 = self._new_k0(kwargs)
         self.rgbnet = None
         if rgbnet_dim > 0:
             self.act_type, self.mode_type = kwargs['act_type'], kwargs['mode_type']      # required upstream (lib/dmpigo.py:89)
@@ -99,6 +99,18 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
     def _new_grid(self, kind, channels, config):
         return grid.create_grid(kind, channels=channels, world_size=self.world_size, xyz_min=self.xyz_min,
                                 xyz_max=self.xyz_max, config=config)
+
+    def _new_k0(self, kwargs):
+        """The colour feature field (lib/dmpigo.py:65-77); `kwargs`: the constructor's extra keyword arguments (lib/dvqgo.DirectQVGO reads n_cluster)."""
+        return self._new_grid(self.k0_type, self.k0_dim, self.k0_config)
+
+    def _k0_features(self, ray_pts):
+        """The colour features of the shaded samples, [n, k0_dim] (lib/dmpigo.py:336): a lookup in the k0 grid."""
+        vox_emb = self.k0(ray_pts)
+        return vox_emb.unsqueeze(-1) if vox_emb.dim() == 1 else vox_emb
+
+    def _scale_k0(self):
+        self.k0.scale_volume_grid(self.world_size)
 
     def _init_act_shift(self, xyz_min, xyz_max):
         """Per-plane density bias chosen so that a ray through an empty volume sees equal alphas on every plane
@@ -150,7 +162,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         the grid is small enough (<= 256^3), refresh the occupancy: old mask looked up at the new nodes AND max-pooled alpha > thres."""
         self._set_grid_resolution(num_voxels, mpi_depth)
         self.density.scale_volume_grid(self.world_size)
-        self.k0.scale_volume_grid(self.world_size)
+        self._scale_k0()
         if int(np.prod(self.world_size.tolist())) <= 256 ** 3:
             nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
             dens = self.density.get_dense_grid() + self.act_shift.grid        # [1,1,X,Y,Z] + [1,1,1,1,D] (D == Z here)
@@ -360,9 +372,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
             if self.fast_color_thres > 0:
                 mask3 = (weights > self.fast_color_thres)
                 ray_pts, ray_id, step_id, alpha, weights = _take(mask3, ray_pts, ray_id, step_id, alpha, weights)
-        vox_emb = self.k0(ray_pts)
-        if vox_emb.dim() == 1:
-            vox_emb = vox_emb.unsqueeze(-1)
+        vox_emb = self._k0_features(ray_pts)
         fused_in = None
         if self.rgbnet is not None and _FUSED_MLP_INPUT:                  # the 16 ops below in one launch (lib/train_ops.RgbnetInputMPI: same values)
             fused_in = train_ops.rgbnet_input_mpi(vox_emb, ray_pts, viewdirs, ray_id, self.xyz_min, self.xyz_max, self.posfreq, self.viewfreq)

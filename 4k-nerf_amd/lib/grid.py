@@ -4,7 +4,8 @@
 arguments, parameter / buffer names (``grid``, ``xyz_min``, ``xyz_max``, ``mask``, ``xyz2ijk_scale``,
 ``xyz2ijk_shift``) and forward semantics; the lookups run on the gfx950 kernels of lib4k_hip.so.
 ``TensoRFGrid`` (lib/grid.py:157-268): the vector-matrix factored grid, its lookup / backward / dense expansion / total variation on the
-kernels of csrc/k4_tensorf.hip.  ``VQGrid`` is not selected by any configuration (configs/default.py:85-86) and is not provided.
+kernels of csrc/k4_tensorf.hip.  ``VQGrid`` (lib/grid.py:38-103): a codebook of feature vectors behind a two-layer projection of the embedded position, the
+nearest codeword found and the codebook's moving average updated on the kernels of csrc/k4_vq.hip.
 """
 
 import math
@@ -123,6 +124,15 @@ def grid_sample_3d_backward(go, C_, X, Y, Z, pts, xyz_min, xyz_max, gg, taker=No
     The image must be all-zero on entry (K4Error while it holds another grid's pending sums) and is left all-zero by the sweep."""
     L = N.lib()
     n = pts.shape[0]
+    if taker is not None and getattr(taker.owner, 'ordered_grad', False) and C_ == 1:
+        # a fixed summation order instead of the atomic scatter (DenseGrid.ordered_grad; lib/dvqgo.py): the samples' terms sorted by voxel, stably
+        vox = torch.empty([n * 8 + 1], dtype=torch.int64, device=go.device)
+        term = torch.empty([n * 8 + 1], dtype=torch.float32, device=go.device)
+        N.check(L.k4_grid_sample_3d_backward_terms(N.f32(go), X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.ptr(vox), N.f32(term), N.stream()),
+                'k4_grid_sample_3d_backward_terms')
+        key, order = torch.sort(vox[:n * 8], stable=True)
+        N.check(L.k4_sorted_segment_add(N.ptr(key), N.f32(term[:n * 8].index_select(0, order)), n * 8, X * Y * Z, N.f32(gg), N.stream()), 'k4_sorted_segment_add')
+        return
     img = _scratch_image(go.device, C_, X, Y, Z, taker) if n > 0 else None
     if img is not None:
         img.run(lambda: N.check(L.k4_grid_sample_3d_backward_cl(N.f32(go), C_, X, Y, Z, N.f32(pts), N.f32(xyz_min), N.f32(xyz_max), n, N.f32(gg), N.ptr(img.ws),
@@ -334,7 +344,14 @@ def create_grid(type, **kwargs):
         return DenseGrid(**kwargs)
     if type == 'TensoRFGrid':
         return TensoRFGrid(**kwargs)
-    raise NotImplementedError(f'{type}: only DenseGrid and TensoRFGrid are provided (SURVEY.md 2.1 #6)')
+    if type == 'VQGrid':
+        if 'input_dim' not in kwargs:
+            # a model that looks its grids up at positions (density_type / k0_type of DirectVoxGO, DirectMPIGO, ...) asking for a codebook: upstream
+            # fails there too, on the missing constructor argument
+            raise NotImplementedError('VQGrid takes an embedded input of input_dim values and a codebook size as world_size (lib/grid.py:39): it is '
+                                      "DirectQVGO's k0 (lib/dvqgo.py:85-88), not a voxel grid of the other models")
+        return VQGrid(**kwargs)
+    raise NotImplementedError(f'{type}: DenseGrid, TensoRFGrid and VQGrid are provided (lib/grid.py:27-35)')
 
 
 class DenseGrid(nn.Module):
@@ -452,6 +469,10 @@ class DenseGrid(nn.Module):
     def finish_grad_seed(self):
         """After the backward pass: a seed no lookup consumed becomes (or is added to) the gradient."""
         self.grad_route.close()
+
+    # True: the one-channel gradient of a lookup is summed in a fixed order (sorted terms, no atomics) so that a training step repeats bit for bit;
+    # slower than the atomic scatter.  Set by models that promise it (lib/dvqgo.py); other channel counts and the optimizer's sparse routes are as ever.
+    ordered_grad = False
 
     def get_dense_grid(self):
         self.params_ready()
@@ -608,6 +629,160 @@ class TensoRFGrid(nn.Module):
     def extra_repr(self):
         ws = self.world_size.tolist() if torch.is_tensor(self.world_size) else list(self.world_size)
         return f'channels={self.channels}, world_size={ws}, n_comp={self.config["n_comp"]}'
+
+
+class VQProject(torch.autograd.Function):
+    """v = W2 relu(W1 x + b1) + b2 of VQGrid.project_layer (lib/grid.py:54-58,64) on k4_vq_project_fwd; the backward (k4_vq_project_bwd) sums the four
+    parameter gradients in a fixed order and hands the input its gradient only when the input requires one."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        x = x.detach().contiguous()
+        ws = [t.detach().contiguous() for t in (w1, b1, w2, b2)]
+        n, in_dim = x.shape
+        dim = ws[0].shape[0]
+        need = any(ctx.needs_input_grad)
+        h = torch.empty([n, dim], dtype=torch.float32, device=x.device) if need else None
+        v = torch.empty([n, dim], dtype=torch.float32, device=x.device)
+        N.check(N.lib().k4_vq_project_fwd(N.f32(x), n, in_dim, dim, *[N.f32(t) for t in ws], None if h is None else N.f32(h), N.f32(v), N.stream()),
+                'k4_vq_project_fwd')
+        if need:
+            ctx.save_for_backward(x, h, ws[0], ws[2])
+        return v
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_v):
+        x, h, w1, w2 = ctx.saved_tensors
+        n, in_dim = x.shape
+        dim = w1.shape[0]
+        g = grad_v.float().contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gw1, gb1, gw2, gb2 = torch.empty_like(w1), w1.new_empty([dim]), torch.empty_like(w2), w2.new_empty([dim])
+        L = N.lib()
+        wsb = int(L.k4_vq_project_bwd_workspace_bytes(n, in_dim, dim))
+        work = torch.empty([max(wsb, 4) // 4], dtype=torch.float32, device=x.device)
+        N.check(L.k4_vq_project_bwd(N.f32(x), N.f32(h), N.f32(g), n, in_dim, dim, N.f32(w1), N.f32(w2), None if gx is None else N.f32(gx),
+                                    N.f32(gw1), N.f32(gb1), N.f32(gw2), N.f32(gb2), N.f32(work), wsb, N.stream()), 'k4_vq_project_bwd')
+        return gx, gw1, gb1, gw2, gb2
+
+
+class VQAssign(torch.autograd.Function):
+    """(quantize, diff, embed_ind) of lib/grid.py:67-100 for the projected vectors v [n, dim]: the nearest codeword by k4_vq_assign and, with `train`, one
+    moving-average update of the owner's three buffers after the features were taken from the old codebook.  Straight-through: quantize's gradient is
+    v's; diff = mean((e - v)^2) adds 2 (v - e) / numel of its own; the buffers get none."""
+
+    @staticmethod
+    def forward(ctx, v, owner, train):
+        v = v.detach().contiguous()
+        n, dim = v.shape
+        dev = v.device
+        L = N.lib()
+        ne = owner.n_embed
+        ind = torch.empty([n], dtype=torch.int64, device=dev)
+        q = torch.empty([n, dim], dtype=torch.float32, device=dev)
+        diff = torch.empty([], dtype=torch.float32, device=dev)
+        wsb = int(L.k4_vq_assign_workspace_bytes(n, dim, ne, int(train)))
+        work = torch.empty([wsb // 8], dtype=torch.float64, device=dev)
+        N.check(L.k4_vq_assign(N.f32(v), n, dim, N.f32(owner.prepared_codebook()), ne, N.ptr(ind), N.f32(q), N.f32(diff), int(train), N.ptr(work), wsb,
+                               N.stream()), 'k4_vq_assign')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(v, q)
+        if train:
+            owner._ema_update(work, n)
+        ctx.mark_non_differentiable(ind)
+        ctx.set_materialize_grads(False)
+        return q, diff, ind
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_q, g_diff, _g_ind):
+        v, q = ctx.saved_tensors
+        g = g_q
+        if g_diff is not None:
+            # q = v + (e - v) = e up to the last bit
+            d = (v - q) * (g_diff * (2.0 / max(v.numel(), 1)))
+            g = d if g is None else g + d
+        return g, None, None
+
+
+class VQGrid(nn.Module):
+    """Vector-quantised feature field (lib/grid.py:38-103): constructor, buffer / parameter names and semantics of the reference.  ``world_size`` is the
+    number of codewords.  ``forward(ind_norm)`` projects the embedded position (Linear, ReLU, Linear), finds the nearest of the ``n_embed`` codewords and
+    returns ``(v + (e - v), mean((e - v)^2), index)``; with the module in training mode -- whatever the autograd mode, as upstream -- the codebook then
+    moves by one exponential-moving-average step.  Everything runs on csrc/k4_vq.hip; there is no CPU path."""
+
+    def __init__(self, input_dim, channels, world_size, xyz_min, xyz_max, decay=0.99, eps=1e-5, **kwargs):
+        super().__init__()
+        self.dim, self.n_embed, self.decay, self.eps = int(channels), int(world_size), decay, eps
+        for name, val in (('xyz_min', xyz_min), ('xyz_max', xyz_max)):
+            self.register_buffer(name, _vec3(val))
+        embed = torch.randn(self.dim, self.n_embed)
+        self.register_buffer('embed', embed)
+        self.register_buffer('cluster_size', torch.zeros(self.n_embed))
+        self.register_buffer('embed_avg', embed.clone())
+        self.project_layer = nn.Sequential(nn.Linear(input_dim, self.dim), nn.ReLU(), nn.Linear(self.dim, self.dim))
+        if not (1 <= input_dim <= 63 and 1 <= self.dim <= 32 and self.n_embed >= 1):
+            raise NotImplementedError(f'VQGrid(input_dim={input_dim}, channels={channels}, world_size={world_size}): the kernels of csrc/k4_vq.hip cover '
+                                      '1..63 inputs, 1..32 channels and at least one codeword')
+
+    def _flat(self, ind_norm, what):
+        if not ind_norm.is_cuda or not self.embed.is_cuda:
+            raise N.K4Error(f'VQGrid.{what}: input and module must be on the GPU (no CPU path)')
+        return ind_norm.reshape(-1, ind_norm.shape[-1]).float()
+
+    def project(self, ind_norm):
+        """``project_layer(ind_norm)`` (lib/grid.py:64) -> [..., dim]."""
+        l1, l2 = self.project_layer[0], self.project_layer[2]
+        v = VQProject.apply(self._flat(ind_norm, 'project'), l1.weight, l1.bias, l2.weight, l2.bias)
+        return v.reshape(*ind_norm.shape[:-1], self.dim)
+
+    def prepared_codebook(self):
+        """The codebook as k4_vq_assign reads it (codewords contiguous, |e|^2 behind each), cached per version of ``embed``."""
+        e = self.embed
+        key = (e.data_ptr(), e._version, str(e.device))
+        hit = self.__dict__.get('_k4_prepared')
+        if hit is None or hit[0] != key:
+            src = e.detach().float().contiguous()
+            out = torch.empty([int(N.lib().k4_vq_codebook_floats(self.dim, self.n_embed))], dtype=torch.float32, device=e.device)
+            N.check(N.lib().k4_vq_prepare_codebook(N.f32(src), self.dim, self.n_embed, N.f32(out), N.stream()), 'k4_vq_prepare_codebook')
+            hit = self.__dict__['_k4_prepared'] = (key, out)
+        return hit[1]
+
+    def _ema_update(self, work, n):
+        """lib/grid.py:80-93 from the counts and sums k4_vq_assign left in `work`: the three buffers in place, their versions bumped (a kernel's store
+        does not bump them), so the prepared codebook re-keys."""
+        bufs = (self.cluster_size, self.embed_avg, self.embed)
+        if any(b.dtype != torch.float32 or not b.is_contiguous() for b in bufs):
+            raise N.K4Error('VQGrid: the codebook buffers must be contiguous fp32 tensors')
+        N.check(N.lib().k4_vq_update_codebook(N.ptr(work), n, self.dim, self.n_embed, float(self.decay), float(1 - self.decay), float(self.eps),
+                                              float(self.n_embed * self.eps), *[N.f32(b) for b in bufs], N.stream()), 'k4_vq_update_codebook')
+        for b in bufs:
+            torch.autograd.graph.increment_version(b)
+
+    def forward(self, ind_norm):
+        shape = ind_norm.shape[:-1]
+        v = self.project(ind_norm).reshape(-1, self.dim)
+        quantize, diff, embed_ind = VQAssign.apply(v, self, bool(self.training))
+        return quantize.reshape(*shape, self.dim), diff, embed_ind.reshape(*shape)
+
+    def embed_code(self, embed_id):
+        """lib/grid.py:102-103: the codewords of the given indices, [..., dim]."""
+        if not embed_id.is_cuda or not self.embed.is_cuda:
+            raise N.K4Error('VQGrid.embed_code: indices and module must be on the GPU (no CPU path)')
+        return self.embed.t().index_select(0, embed_id.reshape(-1)).reshape(*embed_id.shape, self.dim)
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, val in self.__dict__.items():
+            if k != '_k4_prepared':
+                new.__dict__[k] = copy.deepcopy(val, memo)
+        return new
+
+    def extra_repr(self):
+        return f'channels={self.dim}, n_embed={self.n_embed}, decay={self.decay}'
 
 
 def _mask_from_coarse_checkpoint(path, thres):

@@ -84,9 +84,9 @@ def load_model(model_class, ckpt_path):
 
 def model_from_checkpoint_dict(ckpt):
     """Same as load_model for an in-memory checkpoint dict (synthetic scenes)."""
-    from . import dvgo, dmpigo, dcvgo, dbvgo
+    from . import dvgo, dmpigo, dcvgo, dbvgo, dvqgo
     cls = {'DirectMPIGO': dmpigo.DirectMPIGO, 'DirectVoxGO': dvgo.DirectVoxGO,
-           'DirectContractedVoxGO': dcvgo.DirectContractedVoxGO, 'DirectBiVoxGO': dbvgo.DirectBiVoxGO}[ckpt['model_class']]
+           'DirectContractedVoxGO': dcvgo.DirectContractedVoxGO, 'DirectBiVoxGO': dbvgo.DirectBiVoxGO, 'DirectQVGO': dvqgo.DirectQVGO}[ckpt['model_class']]
     model = cls(**ckpt['model_kwargs'])
     model.load_state_dict(ckpt['model_state_dict'])
     return model

@@ -10,6 +10,7 @@ exercised by both the product modules and the oracle.
   * ``make_lego_checkpoint``  -- DirectVoxGO bounded scene, BASELINE config 1
   * ``make_unbounded_checkpoint`` / ``unbounded_poses`` -- DirectContractedVoxGO (unbounded_inward) scene and its cameras
   * ``make_bivox_checkpoint`` -- DirectBiVoxGO (foreground / background grids) scene on the same cameras
+  * ``make_vq_checkpoint``    -- DirectQVGO (codebook colour features) on the LLFF scene and cameras
   * ``llff_spiral_poses`` / ``lego_pose`` / ``LLFF_K`` -- synthetic cameras
 """
 import math
@@ -358,6 +359,31 @@ def make_bivox_checkpoint(seed=777, num_voxels=160 ** 3, bg_preserve=0.5, bg_use
                      'flip_x': False, 'flip_y': False, 'render_depth': True}
     return {'global_step': 0, 'model_kwargs': kwargs, 'model_state_dict': sd,
             'model_class': 'DirectBiVoxGO', 'render_kwargs': render_kwargs}
+
+
+def make_vq_checkpoint(seed=777, num_voxels=96 * 96 * 64, mpi_depth=64, n_cluster=64, rgbnet_dim=6, rgbnet_width=32, rgbnet_depth=3, spatial_pe=2,
+                       stepsize=1.0, project_gain=4.0, **llff):
+    """DirectQVGO checkpoint (lib/dvqgo.py): the geometry, occupancy and rgbnet of ``make_llff_checkpoint`` (same seed, same density field) with the
+    colour grid replaced by a VQGrid -- ``n_cluster`` unit-normal codewords of ``rgbnet_dim`` channels behind a two-layer projection of the
+    ``3 + 6 spatial_pe`` embedded coordinates whose weights are scaled by ``project_gain``, so that the projected vectors spread over the codebook
+    instead of all choosing the codewords next to the origin.  ``cluster_size`` / ``embed_avg`` are those of a codebook in use (positive counts)."""
+    ck = make_llff_checkpoint(seed=seed, num_voxels=num_voxels, mpi_depth=mpi_depth, rgbnet_dim=rgbnet_dim, rgbnet_width=rgbnet_width,
+                              rgbnet_depth=rgbnet_depth, viewbase_pe=0, spatial_pe=spatial_pe, stepsize=stepsize, **llff)
+    g = _gen(seed + 1000003)
+    sd, kw = ck['model_state_dict'], ck['model_kwargs']
+    del sd['k0.grid']
+    in_dim = 3 + 6 * spatial_pe
+    embed = torch.randn([rgbnet_dim, n_cluster], generator=g)
+    cluster_size = torch.rand([n_cluster], generator=g) * 10 + 1
+    w1, b1 = _linear_init(g, rgbnet_dim, in_dim)
+    w2, b2 = _linear_init(g, rgbnet_dim, rgbnet_dim)
+    sd.update({'k0.embed': embed, 'k0.cluster_size': cluster_size, 'k0.embed_avg': embed * cluster_size,
+               'k0.project_layer.0.weight': w1 * project_gain, 'k0.project_layer.0.bias': b1,
+               'k0.project_layer.2.weight': w2 * project_gain, 'k0.project_layer.2.bias': b2})
+    del kw['dim_rend']                                                   # lib/dvqgo.py:156-174 has no such key
+    kw.update(k0_type='VQGrid', n_cluster=n_cluster)
+    ck['model_class'] = 'DirectQVGO'
+    return ck
 
 
 def unbounded_poses(n_frames=8, dist=0.8, height=0.15):

@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      21      /* 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      22      /* 22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -274,6 +274,13 @@ int k4_segment_sum(const float* src, const int64_t* index, int64_t n_pts, int32_
 int k4_grid_sample_3d_backward(const float* grad_out, int32_t channels, int32_t X, int32_t Y, int32_t Z,
                                const float* xyz, const float* xyz_min, const float* xyz_max, int64_t n_pts,
                                float* grad_grid, void* stream);
+/* ABI 22 -- the ONE-channel gradient in a fixed summation order (a training step that must repeat bit for bit): k4_grid_sample_3d_backward_terms
+ * writes per sample its eight terms, voxel [n_pts][8] (flat index into [X][Y][Z]; -1 where the trilinear weight is 0) and term [n_pts][8] =
+ * grad_out * weight; the caller sorts them by voxel with a STABLE sort; k4_sorted_segment_add then adds every run of equal keys (0 <= key < n_out)
+ * in order and adds the sum to out[key] -- no atomics. */
+int k4_grid_sample_3d_backward_terms(const float* grad_out, int32_t X, int32_t Y, int32_t Z, const float* xyz, const float* xyz_min,
+                                     const float* xyz_max, int64_t n_pts, int64_t* voxel, float* term, void* stream);
+int k4_sorted_segment_add(const int64_t* key, const float* val, int64_t m, int64_t n_out, float* out, void* stream);
 /* The same gradient for channels > 1 through a channel-last scratch image (lanes = (sample, channel): a corner's contributions are
  * consecutive floats, which is what the atomic units are fast at -- 2x on ray-coherent batches, ~10x on random points) and a sweep
  * that moves the touched voxels into grad_grid [C][X][Y][Z] (+=).  `workspace` (k4_grid_sample_3d_backward_workspace_bytes, 16-byte
@@ -951,6 +958,57 @@ int k4_tensorf_sample_backward(const float* grad_out, const float* xy, const flo
 int k4_tensorf_dense(const float* xy, const float* xz, const float* yz, const float* xv, const float* yv, const float* zv, const float* fvec,
                      int32_t C, int32_t R, int32_t Rxy, int32_t X, int32_t Y, int32_t Z, float* out, void* stream);
 int k4_tensorf_tv_add_grad(const float* param, float* grad, int32_t R, int32_t A, int32_t B, float wa, float wb, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 22 -- vector-quantised colour features (csrc/k4_vq.hip): VQGrid of lib/grid.py:38-103.
+ * 1 <= in_dim <= 63, 1 <= dim <= 32, n_embed >= 1; all tensors fp32 row-major as the nn.Linear / buffer tensors are stored
+ * (w1 [dim][in_dim], w2 [dim][dim], embed [dim][n_embed]).  Every result is a function of the inputs alone (fixed summation orders, no atomics).
+ * k4_vq_project_fwd: h [n][dim] = relu(W1 x + b1) (NULL = not wanted), v [n][dim] = W2 h + b2; fp32 FMA chains.
+ * k4_vq_project_bwd: for grad_v [n][dim]: grad_x [n][in_dim] (NULL = not wanted) and the four parameter gradients, OVERWRITTEN with the sums over the
+ *   points: per 2048-point slab in point order, the slabs added in order.  `workspace`: k4_vq_project_bwd_workspace_bytes.
+ * k4_vq_prepare_codebook: prepared [n_embed][stride] (k4_vq_codebook_floats in all) = each codeword contiguous, then |e|^2 (the squares rounded and
+ *   added over the channels in order, as embed.pow(2).sum(0)), padded to 16 bytes.  The caller caches it per version of `embed`.
+ * k4_vq_assign: ind [n] = argmin_e (|v|^2 - (2 v).E_e) + |E_e|^2, the lowest index on an exact tie; quantize [n][dim] = v + (E[ind] - v) in fp32, in that
+ *   order; *diff = mean((E[ind] - v)^2) summed in fp64 in a fixed order (NaN for n == 0, as torch.mean of nothing).  The codebook is walked in chunks of
+ *   k4_vq_chunk_codes(dim) codes staged in LDS, a running best carried across chunks (earlier chunks win ties).  with_stats != 0 also leaves per-code
+ *   counts and per-code sums of v in `workspace` (k4_vq_assign_workspace_bytes; fp64, fixed order) for
+ * k4_vq_update_codebook (same n_pts, dim, n_embed and workspace as the k4_vq_assign call before it), lib/grid.py:80-93 in place:
+ *   cluster_size = cluster_size * decay + one_minus_decay * count;  embed_avg = embed_avg * decay + one_minus_decay * sum;
+ *   embed = embed_avg / ((cluster_size + eps) / (sum(cluster_size) + n_embed_eps) * sum(cluster_size)).  n_pts == 0 keeps this arithmetic (zero counts).
+ * ------------------------------------------------------------------------------------------- */
+int k4_vq_project_fwd(const float* x, int64_t n_pts, int32_t in_dim, int32_t dim, const float* w1, const float* b1, const float* w2, const float* b2,
+                      float* h, float* v, void* stream);
+int64_t k4_vq_project_bwd_workspace_bytes(int64_t n_pts, int32_t in_dim, int32_t dim);      /* <0: unsupported shape */
+int k4_vq_project_bwd(const float* x, const float* h, const float* grad_v, int64_t n_pts, int32_t in_dim, int32_t dim, const float* w1, const float* w2,
+                      float* grad_x, float* gw1, float* gb1, float* gw2, float* gb2, float* workspace, int64_t workspace_bytes, void* stream);
+int64_t k4_vq_codebook_floats(int32_t dim, int32_t n_embed);
+int32_t k4_vq_chunk_codes(int32_t dim);
+int k4_vq_prepare_codebook(const float* embed, int32_t dim, int32_t n_embed, float* prepared, void* stream);
+int64_t k4_vq_assign_workspace_bytes(int64_t n_pts, int32_t dim, int32_t n_embed, int32_t with_stats);
+int k4_vq_assign(const float* v, int64_t n_pts, int32_t dim, const float* prepared, int32_t n_embed, int64_t* ind, float* quantize, float* diff,
+                 int32_t with_stats, void* workspace, int64_t workspace_bytes, void* stream);
+int k4_vq_update_codebook(const void* workspace, int64_t n_pts, int32_t dim, int32_t n_embed, float decay, float one_minus_decay, float eps,
+                          float n_embed_eps, float* cluster_size, float* embed_avg, float* embed, void* stream);
+
+/* ABI 22 -- DirectQVGO inference in ONE launch (lib/dvqgo.py:279-408 under torch.no_grad, module in eval mode).  One wave per ray, lanes = 64 consecutive
+ * samples in depth order.  Geometry: DirectMPIGO's three filters with the arithmetic of the staged ops (k4_train_select_mpi), so the decisions are
+ * theirs.  Survivors are queued on chip and shaded 64 at a time: positional embedding (n_pe frequencies), the projection (pw1 [dim][3 + 6 n_pe], pw2
+ * [dim][dim]), the codeword search over `codebook` (k4_vq_prepare_codebook's output for n_embed codes of dim channels) with k4_vq_assign's
+ * expressions, v + (e - v), the rgbnet (w1 [width][dim0], dim0 = dim + 3 + 6 n_pe + 3: [vq_emb | pe_emb | viewdirs]; width 32 | 64 | 128, n_hidden
+ * 0 | 1; w2 / b2 NULL without a hidden layer), sigmoid.  Per ray: rgb [n][3] (+ alphainv_last * bg), depth [n] = sum w (step + 0.5) / n_samples,
+ * alphainv_last [n].  Nothing per sample is written to memory.  xyz_min / xyz_max / xyz2ijk_* are DEVICE pointers to 3 floats; mask: uint8 [mask_dims].
+ * Other widths: K4_ERR_UNSUPPORTED (the staged ops cover them). */
+typedef struct k4_vq_desc {
+    const float* rays_o; const float* rays_d; const float* viewdirs; int64_t n_rays; int32_t n_samples;
+    const float* density; int32_t dims[3]; const float* act_shift; int32_t act_depth; const float* xyz_min; const float* xyz_max;
+    const uint8_t* mask; int32_t mask_dims[3]; const float* xyz2ijk_scale; const float* xyz2ijk_shift;
+    float interval; float fast_color_thres; float bg;
+    const float* posfreq; int32_t n_pe;
+    const float* pw1; const float* pb1; const float* pw2; const float* pb2; int32_t dim; const float* codebook; int32_t n_embed;
+    const float* w1; const float* b1; const float* w2; const float* b2; const float* w3; const float* b3; int32_t dim0; int32_t width; int32_t n_hidden;
+    float* rgb; float* depth; float* alphainv_last;
+} k4_vq_desc;
+int k4_march_vq_fwd(const k4_vq_desc* desc, void* stream);
 
 #ifdef __cplusplus
 }
