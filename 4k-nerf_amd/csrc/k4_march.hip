@@ -20,7 +20,9 @@
 //     transposed (lane = ray) by whichever wave of the workgroup finishes its quarter last (an LDS arrival counter, no barrier).
 //     Survivors (w > thres) go to the front of the bundle's slice of a workspace as 8-byte {ray,step | weight} records -- ~9
 //     per ray instead of the reference's 256 x 60 B of per-sample intermediates: appended by the scan itself in the FAST
-//     (LLFF) instantiation, compacted in place by a second pass over the records in the general one.
+//     (LLFF) instantiation, compacted in place by a second pass over the records in the general one.  FAST also deals the
+//     16-sample groups of every ray round-robin over the 4 waves instead of a depth quarter each (k4_geom_deal.h): a
+//     scene's content sits in a few neighbouring groups, and with quarters one wave carried 2.4x the mean load.
 // K2  k4_shade_kernel  (VALU / gather bound)
 //     persistent waves pull bundles from a queue; 64 records at a time, lane = sample: 8-corner k0 gather from the
 //     channel-last repack, features to LDS, then the rgbnet MLP on the matrix cores as C^T[neuron][sample] = W . X --
@@ -34,6 +36,7 @@
 // LDS-DMA prefetch of the next batch's gathers at one workgroup per CU) were measured and dropped: DESIGN.md 5, profiles/.
 // Deterministic: no global atomics on the data path, fixed summation order.
 #include "k4_common.h"
+#include "k4_geom_deal.h"
 #include <string.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -73,7 +76,7 @@ struct MarchParams {
     int serp;               // 1: serpentine ray order inside a tile (default)
     int band_blocks;        // geometry kernel: blocks per XCD band (0: one contiguous band per XCD)
     float* out_rgb; float* out_depth; float* out_ainv; unsigned long long* counters;
-    unsigned long long* timing;     // K4_GEOM_TIMING builds: [9] stage ticks + wave count (the kernel runs WITHOUT the counting instantiation)
+    unsigned long long* timing;     // K4_GEOM_TIMING builds: [8] stage ticks, wave count, [9..11] wave life / first start / last end on the wall clock (the kernel runs WITHOUT the counting instantiation)
 };
 
 template <int MODE>
@@ -162,6 +165,11 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 //   FAST instantiation: C and D are ONE pass -- the scan appends a survivor to the front of the slice the moment it has its weight
 //   (no write-back of w, no second read of the records; a stopped ray reads nothing more).  The raw runs therefore start one quarter
 //   into the slice; the shading kernel does not care about the order of a bundle's records.
+//   FAST instantiation, the deal (k4_geom_deal.h; tools/geom_deal_model.py, profiles/geom_wave_deal.md): group G of ray slot r belongs to wave
+//   (G + (r >> 4)) & 3, so wave w's slot j = 0..3 of ray r is group 4 j + ((w - (r >> 4)) & 3) in depth quarter j -- still at most 4 groups of a
+//   ray per wave.  P probes those groups; the entry list of A is slot-major, then ray, so a wave emits its records in depth-quarter order; B files
+//   a record by k >> 6 into the wave's own segment (quarter / 4 records) of slice quarter (k >> 6) + 1 and counts it in an 8-bit field of
+//   acnt[ray]; the tail reads ray r's records of quarter j as its pieces of the segments of waves (i + (r >> 4)) & 3, i = 0..3.
 // -----------------------------------------------------------------------------------------------------
 #ifndef K4_GEOM_MIN_WG
 #define K4_GEOM_MIN_WG 1
@@ -182,9 +190,10 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 #define K4_GEOM_DEBUG_BITS (16 | 32 | 128 | 4096 | 8192)      // the K4_DEBUG ablation bits the geometry kernel reads (general instantiation only)
 struct Geom2Lds {
     float raytab[64][8];     // [0..2] start xyz, [3] bits(kq0) | [4..6] dir xyz, [7] bits(kq1): the bundle's rays and THIS wave's depth range [kq0,kq1) of each
+                             // (FAST: [3] = the wave's group offset (w - (r >> 4)) & 3 inside every depth quarter of the ray, [7] = nsteps)
     unsigned qk[K4_RING];    // ring of mask-passing samples: ray_local<<24 | step (residual < 64 + one group of 256)
-    int acnt[64];            // alpha-passing samples per ray
-    unsigned short elist[K4_ELIST];   // kept entries, ray-major / depth-ascending: ray_local<<10 | group
+    int acnt[64];            // alpha-passing samples per ray (FAST: four 8-bit fields, one per slot = depth quarter, each <= 16)
+    unsigned short elist[K4_ELIST];   // kept entries, ray-major / depth-ascending: ray_local<<10 | group (FAST: slot-major, then ray: ray_local<<10 | slot)
 };
 
 template <int MODE>
@@ -197,6 +206,8 @@ __device__ __forceinline__ float tk_of(const MarchParams& P, const float* tktab,
 // two neighbouring rays is 4 rows x 256 B: the row reuse of adjacent rays hits L1/L2).  Records of quarter w go to quarter w of
 // the bundle's workspace slice (FAST: quarter w + 1, the first quarter takes the survivors); the last wave to finish its quarter
 // runs the transmittance scan over the four runs of each ray in depth order and compacts the survivors (no barrier).
+// FAST deals GROUPS instead (k4_geom_deal.h, stage list above): every wave works in all four depth quarters, slice quarter j + 1 holds depth
+// quarter j as four per-wave segments, and the four waves finish close together -- the workgroup's LDS is no longer held by one straggler.
 // COUNT: the sample counters of bench.py / the tests (k4_march_*_fwd `counters`) are a separate instantiation that visits EVERY
 // sample (no skipping), so that the counters are the algorithm's sample counts and the render path carries no
 // counting code.
@@ -212,13 +223,16 @@ __device__ __forceinline__ float tk_of(const MarchParams& P, const float* tktab,
 // kernel's FAST -- MPI render instantiation, interval == 1 and thres > 0 (one raw2alpha form, both filters on), ONE launch (no slab arithmetic),
 // occupancy summary present, n_samples <= K4_TKTAB (=> at most 4 groups per ray and depth quarter: never `big`, one ray batch; every k a lane can
 // form, the padding lanes of a last group included, is below roundup16(n_samples) <= K4_TKTAB: step positions come from the table without the
-// division fallback and its branch), Z >= 2, no ablation bit.  It only drops code these conditions make dead: every expression tree is the general
-// path's -> the same bits (tests/test_geom_fast_gpu.py).  The host predicate is in launch_march; K4_DEBUG & 16384 forces the general path.
+// division fallback and its branch), Z >= 2, no ablation bit.  It drops code these conditions make dead and deals the groups to other waves (above):
+// every expression tree of a sample is the general path's and a ray's records reach the scan in the same depth order -> the same bits
+// (tests/test_geom_fast_gpu.py, test_geom_tail_gpu.py, test_geom_deal_gpu.py).  Bounded for 7 waves per SIMD (71 VGPRs, no spill): its residency
+// is the 7 workgroups per CU that 22.5 KB of LDS admit.  The host predicate is in launch_march; K4_DEBUG & 16384 forces the general path.
 template <int MODE, bool COUNT, int MINW, bool FAST = false>
-__global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P) {
+__global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const MarchParams P) {
     static_assert(!FAST || (MODE == MODE_MPI && !COUNT), "FAST is the MPI render instantiation");
 #ifdef K4_GEOM_TIMING
     unsigned long long gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, glast = __builtin_amdgcn_s_memtime();
+    const unsigned long long gwall0 = wall_clock64();                  // constant-rate clock shared by the whole device: wave life against the kernel's span
 #endif
     __shared__ Geom2Lds lds_all[4];
     __shared__ int na_sh[4];
@@ -287,6 +301,12 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
             kq0 = P.split_k + wv * span1; kq1 = alive ? min(kq0 + span1, nsteps) : kq0;
         }
         ngrp = kq1 > kq0 ? (kq1 - kq0 + K4_GRP - 1) / K4_GRP : 0;
+        if constexpr (FAST) {
+            // the deal (k4_geom_deal.h): this wave's slot j of the ray is group 4 j + off; the slots whose group starts below nsteps are j < ngrp
+            kq0 = k4_deal_offset(wv, lane); kq1 = nsteps;
+            const int ng = (nsteps + K4_GRP - 1) / K4_GRP;
+            ngrp = ng > kq0 ? (ng - kq0 + 3) >> 2 : 0;
+        }
         *reinterpret_cast<float4*>(&L.raytab[lane][0]) = make_float4(sx, sy, sz, __int_as_float(kq0));
         *reinterpret_cast<float4*>(&L.raytab[lane][4]) = make_float4(dx, dy, dz, __int_as_float(kq1));
         L.acnt[lane] = 0;
@@ -315,7 +335,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
         const int ntab = ((P.MX + K4_OCC_CELL - 1) >> K4_OCC_SHIFT) * ncy * zw;                // entries per table
 #pragma unroll 4
         for (int j = 0; j < gq; ++j) {                                            // (unrolled: the summary fetches of 4 groups fly together)
-            const int ka = kq0 + K4_GRP * j, kb = min(ka + K4_GRP - 1, kq1 - 1);
+            const int ka = FAST ? K4_GRP * (4 * j + kq0) : kq0 + K4_GRP * j, kb = min(ka + K4_GRP - 1, kq1 - 1);
             const float ta = tk_at(j < ngrp ? ka : 0), tb = tk_at(j < ngrp ? kb : 0);
             // the two end samples, with the arithmetic of stage A (same fmaf chain, same round())
             const int iax = k4_round_half_away(fmaf(fmaf(rb.x, ta, ra.x), P.msx, P.mtx)), ibx = k4_round_half_away(fmaf(fmaf(rb.x, tb, ra.x), P.msx, P.mtx));
@@ -343,6 +363,8 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     K4_GSTAMP(1);                                                                // stage P: probe
     int qn = 0, qh = 0;          // ring fill / head (wave-uniform)
     int na = 0;                  // alpha-passing records written so far (wave-uniform)
+    int nq0 = 0, nq1 = 0, nq2 = 0, nq3 = 0;      // FAST: ... per depth quarter, = the fill of this wave's four segments
+    const int seg0 = (int)k4_deal_seg_base(wv, 0, quarter);      // FAST: this wave's segment of depth quarter 0, in records from ent_base
 
     // ---- stage B: density + activation, lane = sample, up to 2 ring entries per lane.  Split in two halves so that the
     // 8 corner fetches of a batch are in flight while the wave does the occupancy stage of the NEXT 256 samples: the
@@ -430,12 +452,27 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
             if (unit_interval) alpha = 1.f - 1.f / (1.f + e);
             else alpha = 1.f - powf(1.f + e, -P.interval);
             const bool act = lact && (use_thres ? (alpha > P.thres) : true);
-            const uint64_t bm = __ballot(act);
-            if (act) {
-                ent[na + k4_prefix(bm)] = make_uint2(key, __float_as_uint(alpha));
-                atomicAdd(&L.acnt[(int)(key >> 24)], 1);
+            if constexpr (FAST) {
+                // a batch can hold records of several depth quarters (the ring is slot-major): one ballot per quarter present, each record to
+                // its quarter's segment of this wave at the segment's running count
+                const int qd = (int)(key & 0xffffffu) >> 6;
+                int dst = 0;
+#define K4_DEAL_PUT(Q, NQ) do { const uint64_t bq_ = __ballot(act && qd == Q); \
+                                if (bq_ != 0ull) { if (qd == Q) dst = seg0 + Q * quarter + NQ + (int)k4_prefix(bq_); NQ += __popcll(bq_); } } while (0)      /* (wave-uniform) */
+                K4_DEAL_PUT(0, nq0); K4_DEAL_PUT(1, nq1); K4_DEAL_PUT(2, nq2); K4_DEAL_PUT(3, nq3);
+#undef K4_DEAL_PUT
+                if (act) {
+                    ent_base[dst] = make_uint2(key, __float_as_uint(alpha));
+                    atomicAdd(&L.acnt[(int)(key >> 24)], 1 << (8 * qd));
+                }
+            } else {
+                const uint64_t bm = __ballot(act);
+                if (act) {
+                    ent[na + k4_prefix(bm)] = make_uint2(key, __float_as_uint(alpha));
+                    atomicAdd(&L.acnt[(int)(key >> 24)], 1);
+                }
+                na += __popcll(bm);
             }
-            na += __popcll(bm);
         }
         pend_n = 0;
     };
@@ -456,7 +493,17 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     if (!FAST) while (rb > 1 && rb * gq > K4_ELIST) rb >>= 1;
     for (int r0 = 0; r0 < 64; r0 += rb) {
         int total;
-        {
+        if constexpr (FAST) {
+            // slot-major, then ray: a wave emits its records in depth-quarter order, ray-major inside a quarter.  Positions by one ballot per slot
+            total = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool kj = ((keep >> j) & 1ull) != 0ull;
+                const uint64_t bj = __ballot(kj);
+                if (kj) L.elist[total + (int)k4_prefix(bj)] = (unsigned short)((lane << 10) | j);
+                total += __popcll(bj);
+            }
+        } else {
             const bool mine = lane >= r0 && lane < r0 + rb;
             int c = mine ? (big ? ngrp : __popcll(keep)) : 0;
             int incl = c;
@@ -491,7 +538,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
                 const int r_ = (int)(e >> 10), g_ = (int)(e & 1023u);
                 const float4 ra = *reinterpret_cast<const float4*>(&L.raytab[r_][0]);
                 const float4 rbv = *reinterpret_cast<const float4*>(&L.raytab[r_][4]);
-                const int k = __float_as_int(ra.w) + g_ * K4_GRP + l15;
+                const int k = FAST ? K4_GRP * (4 * g_ + __float_as_int(ra.w)) + l15 : __float_as_int(ra.w) + g_ * K4_GRP + l15;
                 const float tk = tk_at(k);
                 const float px = fmaf(rbv.x, tk, ra.x), py = fmaf(rbv.y, tk, ra.y), pz = fmaf(rbv.z, tk, ra.z);
                 const bool inb = ev && (k < __float_as_int(rbv.w)) &&
@@ -526,11 +573,12 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
     while (qn > 0) { issue_b(min(qn, 128)); finish_b(); }
     K4_GSTAMP(6);                                                                // drain
 
-    // No barrier: a wave whose quarter is done leaves at once (depth quarters are very unequal -- waves parked at a barrier held 1/3
-    // of the wave slots); the LAST wave to arrive finishes the bundle.  It re-reads records the other waves stored: every wave drains
+    // No barrier: a wave whose share is done leaves at once (depth quarters are very unequal -- waves parked at a barrier held 1/3
+    // of the wave slots; FAST deals groups instead and its waves arrive close together); the LAST wave to arrive finishes the bundle.  It re-reads records the other waves stored: every wave drains
     // its stores (vmcnt) before it counts itself in, the records go through this CU's L1 write-through and were never read before.
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     int prev = 0;
+    if constexpr (FAST) na = nq0 + nq1 + nq2 + nq3;
     if (lane == 0) { na_sh[wv] = na; prev = __hip_atomic_fetch_add(&arrived, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP); }
     prev = __builtin_amdgcn_readfirstlane(prev);
     if (prev != 3) break;                                              // not the last: done
@@ -545,36 +593,58 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
         // ray's records in it: one 8-byte load of the raw {key, alpha} (the next four ranks are requested before the current four are
         // folded into T), the reference's sequential product, a ballot over the 64 rays and one coalesced 8-byte store per surviving
         // lane.  No weight goes back to the raw run and nothing is read twice; a ray that has stopped loads nothing more, and the pass
-        // ends when no ray has both records left and transmittance left.  Record order of a bundle: quarter, rank within the ray, ray
-        // slot (the general path: quarter, ray, depth) -- the shading kernel's per-ray sums are exact integer adds and a sample's MLP
+        // ends when no ray has both records left and transmittance left.  The records of quarter w lie in four per-wave segments (the deal);
+        // the rank of a record within its ray counts through the ray's four pieces in depth order, so the step count of a quarter stays
+        // ceil(max_r c / 4).  Record order of a bundle: quarter, rank within the ray, ray slot (the general path: quarter, ray, depth) -- the shading kernel's per-ray sums are exact integer adds and a sample's MLP
         // column does not depend on its lane or batch, so the pixels are the same bits (tests/test_geom_tail_gpu.py).
         // No hazard between the appends and the raw records still to be read:
-        //   - a wave's run holds na_v <= quarter records (FAST: one 64-sample block per ray and quarter, 64 rays), and survivors are a
-        //     subset of the records already read: while quarter w is scanned every append lands below sum_{v<=w} na_v <= (w + 1) * quarter;
-        //   - every raw record not yet read lies at or above (w + 1) * quarter, where run w starts;
+        //   - depth quarter v holds n_v <= quarter records (64 rays x one 64-sample block; each of its four segments <= quarter / 4), and
+        //     survivors are a subset of the records already read: while quarter w is scanned every append lands below
+        //     sum_{v<=w} n_v <= (w + 1) * quarter;
+        //   - every raw record not yet read lies at or above (w + 1) * quarter, where the first segment of depth quarter w starts;
         //   - the largest index ever written is (w + 1) * quarter - 1, reached only when every sample of every ray survives.
         // So the two regions never meet and the pointers below do not alias.
         uint2* __restrict__ const surv = ent_base;
+        const uint2* __restrict__ const raw = ent_base;
         const bool any_rec = (na_sh[0] | na_sh[1] | na_sh[2] | na_sh[3]) != 0;              // (wave-uniform) a bundle without records: nothing to scan
+        const int skew = k4_deal_skew(lane);
 #pragma unroll
-        for (int w = 0; w < 4 && any_rec; ++w) {
+        for (int w = 0; w < 4 && any_rec; ++w) {                       // depth quarter w
             if (__ballot(!stopped) == 0ull) break;                     // every ray has stopped: the remaining quarters are behind the stop
-            const uint2* __restrict__ const run = ent_base + (size_t)(w + 1) * quarter;
-            const int c = lds_all[w].acnt[lane];
-            int incl = c;
+            // Ray `lane`'s records of the quarter are four pieces, one in the segment of each wave, in the depth order i = 0..3 of the waves
+            // (i + skew) & 3 (k4_geom_deal.h).  A piece starts at the exclusive prefix over the rays of that (wave, slot) count: two scans of
+            // 16-bit pairs (a segment holds <= 1024 records).  pk[v] = count | prefix << 8 of wave v, then rotated so that pk[i] is piece i's.
+            const int cv0 = (lds_all[0].acnt[lane] >> (8 * w)) & 0xff, cv1 = (lds_all[1].acnt[lane] >> (8 * w)) & 0xff;
+            const int cv2 = (lds_all[2].acnt[lane] >> (8 * w)) & 0xff, cv3 = (lds_all[3].acnt[lane] >> (8 * w)) & 0xff;
+            const int p01 = cv0 | (cv1 << 16), p23 = cv2 | (cv3 << 16);
+            int i01 = p01, i23 = p23;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
-                const int v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
+                const int v01 = __shfl_up(i01, off), v23 = __shfl_up(i23, off);
+                if (lane >= off) { i01 += v01; i23 += v23; }
             }
-            const uint2* __restrict__ const mine = run + (incl - c);   // this ray's records of the quarter, depth-ascending
+            i01 -= p01; i23 -= p23;
+            const int u0 = cv0 | ((i01 & 0xffff) << 8), u1 = cv1 | ((i01 >> 16) << 8), u2 = cv2 | ((i23 & 0xffff) << 8), u3 = cv3 | ((i23 >> 16) << 8);
+            const bool s1 = (skew & 1) != 0, s2 = (skew & 2) != 0;
+            const int t0 = s1 ? u1 : u0, t1 = s1 ? u2 : u1, t2 = s1 ? u3 : u2, t3 = s1 ? u0 : u3;
+            const int pk0 = s2 ? t2 : t0, pk1 = s2 ? t3 : t1, pk2 = s2 ? t0 : t2, pk3 = s2 ? t1 : t3;
+            // rank t of the ray lies at raw[t + (t < a0 ? b0 : t < a1 ? b1 : t < a2 ? b2 : b3)]: a = running piece ends, b = piece start - ranks before it
+            const int qseg = quarter >> 2, qbase = (w + 1) * quarter;
+            const int a0 = pk0 & 0xff, a1 = a0 + (pk1 & 0xff), a2 = a1 + (pk2 & 0xff), c = a2 + (pk3 & 0xff);
+            const int b0 = qbase + ((0 + skew) & 3) * qseg + (pk0 >> 8);
+            const int b1 = qbase + ((1 + skew) & 3) * qseg + (pk1 >> 8) - a0;
+            const int b2 = qbase + ((2 + skew) & 3) * qseg + (pk2 >> 8) - a1;
+            const int b3 = qbase + ((3 + skew) & 3) * qseg + (pk3 >> 8) - a2;
+            // (the empty asm keeps the three selects apart: folded into one expression the compiler turns them into a table in scratch)
+            auto rec_at = [&](int t) -> int { int d = t < a2 ? b2 : b3; asm volatile("" : "+v"(d)); d = t < a1 ? b1 : d; asm volatile("" : "+v"(d));
+                                              return t + (t < a0 ? b0 : d); };
             // Software pipeline, one step = four ranks: [wait for this step's records] [store the PREVIOUS step's survivors] [request the
             // next step's records] [fold this step into T].  Loads and stores sit in exec-mask branches, so the compiler cannot count
             // them: any wait it places behind them is vmcnt(0).  In this order the only wait of a step comes first, when nothing
             // younger than the records it needs is in flight -- the next step's loads and this step's stores fly under the arithmetic.
             uint2 en[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) en[u] = (u < c && !stopped) ? mine[u] : make_uint2(0u, 0u);
+            for (int u = 0; u < 4; ++u) en[u] = (u < c && !stopped) ? raw[rec_at(u)] : make_uint2(0u, 0u);
             uint2 pe[4];                                               // survivors of the previous step: {key, weight} ...
             int ppos[4];                                               // ... and where they go
             bool pshade[4] = {false, false, false, false};
@@ -588,7 +658,7 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
                 for (int u = 0; u < 4; ++u) if (pshade[u]) surv[ppos[u]] = pe[u];
                 if (!more) break;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) en[u] = (j0 + 4 + u < c && !stopped) ? mine[j0 + 4 + u] : make_uint2(0u, 0u);
+                for (int u = 0; u < 4; ++u) en[u] = (j0 + 4 + u < c && !stopped) ? raw[rec_at(j0 + 4 + u)] : make_uint2(0u, 0u);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -700,6 +770,9 @@ __global__ __launch_bounds__(256, MINW) void k4_geom3_kernel(const MarchParams P
 #pragma unroll
         for (int i = 0; i < 8; ++i) atomicAdd(&P.timing[i], gacc[i]);
         atomicAdd(&P.timing[8], 1ull);
+        const unsigned long long gwall1 = wall_clock64();
+        atomicAdd(&P.timing[9], gwall1 - gwall0);                      // [9] summed wave life, [10] first start (the caller presets it to a large value), [11] last end
+        atomicMin(&P.timing[10], gwall0); atomicMax(&P.timing[11], gwall1);
     }
 #endif
     if (COUNT && P.counters && lane == 0) {
@@ -1148,15 +1221,18 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
     {
         // one workgroup (4 waves = 4 depth quarters) per bundle
         // MINW = waves per SIMD the register allocation is bounded for: 5 (general path: 96 VGPRs, 4 spilled; 6 = 80 VGPRs spills 17 registers, measured
-        // 3 % slower in round 3).  FAST takes 72 VGPRs without a spill since its tail is one pass (85 before: profiles/geom_fast_path.md), so its
-        // residency is set by the 22 KB of LDS -- 7 workgroups per CU -- and no longer by the bound (profiles/geom_tail_append.md)
+        // 3 % slower in round 3).  FAST is bounded for 7 by the kernel itself (71 VGPRs without a spill; the segment walker of its tail came to 73
+        // under the bound of 5): its residency is set by the 22 KB of LDS -- 7 workgroups per CU (profiles/geom_tail_append.md, geom_wave_deal.md)
         // FAST: the LLFF configuration (see k4_geom3_kernel); anything else -- DVGO, the counting instantiation, a split scene, stepsize != 1,
         // a scene without the occupancy summary, more than K4_TKTAB samples, any ablation bit the kernel reads -- takes the general instantiation
         const bool gfast = MODE == MODE_MPI && !P.counters && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr &&
                            P.Z >= 2 && P.n_samples <= K4_TKTAB && (P.debug & K4_GEOM_DEBUG_BITS) == 0 && !k4_env().no_fast_geom;
 #ifdef K4_GEOM_TIMING
-        if (P.counters) { MarchParams Q = P; Q.timing = P.counters + 8; Q.counters = nullptr;
-                          hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q); } else
+        if (P.counters) { MarchParams Q = P; Q.timing = P.counters + 8; Q.counters = nullptr;       // the instantiation the render path would take
+                          const bool tfast = MODE == MODE_MPI && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr && P.Z >= 2 &&
+                                             P.n_samples <= K4_TKTAB && (P.debug & K4_GEOM_DEBUG_BITS) == 0 && !k4_env().no_fast_geom;
+                          if (tfast) hipLaunchKernelGGL((k4_geom3_kernel<MODE_MPI, false, 5, true>), dim3((unsigned)nwg * 4), block, 0, st, Q);
+                          else hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q); } else
 #endif
         if (P.counters) hipLaunchKernelGGL((k4_geom3_kernel<MODE, true, 5>), dim3((unsigned)nwg * 4), block, 0, st, P);
         else if (MODE == MODE_MPI && P.split_k > 0) {
@@ -1217,7 +1293,7 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
 static inline int64_t ent_quarter_of(int32_t max_steps) { return 16 * (((int64_t)max_steps + 255) / 256 * 256); }
 // records per bundle: FIVE quarters.  General instantiation: the four waves' runs of alpha-passing records in quarters 0..3, survivors
 // compacted in place to the front, quarter 4 unused.  FAST instantiation: survivors appended from the front of quarter 0 while the
-// runs are read from quarters 1..4 (see the kernel's tail).  Either way the shading kernel reads records [0, counts[b]) of the slice.
+// raw records are read from quarters 1..4 -- depth quarter j in slice quarter j + 1, four per-wave segments each (k4_geom_deal.h; the kernel's tail).  Either way the shading kernel reads records [0, counts[b]) of the slice.
 static inline int64_t ent_stride_of(int32_t max_steps) { return 5 * ent_quarter_of(max_steps); }
 
 // workspace: [records nb x ent_stride x 8 B][counts nb] | [queue head .. queue length: 64 ints] | [jobs: nb x 8 B], each 256-aligned
