@@ -6,6 +6,7 @@
 // All are HBM-streaming, one thread per element (or one WAVE per ray for the transmittance scan).
 #include "k4_common.h"
 #include "k4_vq.h"
+#include "k4_ray_walk.h"
 
 #define K4_THREADS 256
 static inline unsigned k4_blocks(int64_t n) { return (unsigned)((n + K4_THREADS - 1) / K4_THREADS); }
@@ -1089,47 +1090,35 @@ extern "C" int k4_to8b(const float* x, int64_t n, uint8_t* out, void* stream) {
     hipLaunchKernelGGL(k_to8b, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, x, n, out);
     return k4_check_launch();
 }
-// ---------------------------------------------------------------- DirectContractedVoxGO inference: ONE launch per call (k4_march_contracted_fwd)
-// The staged forward (lib/dcvgo.py) materialises an [N][n_max][3] point table (1,068 steps per ray at 320^3) and filters it three times with host
-// synchronisations.  Here one WAVE walks one ray, lanes = 64 consecutive steps, in depth order, and nothing per sample leaves the chip:
-//   point     p_k = o' + d' t_tab[k], o' = (o - c) / r, d' = d / |d|; norm (inf | l2); outside the unit ball p <- p / n ((1 + bg) - n^-1 bg)
-//             (torch's `bg_len / norm` is reciprocal * bg_len) -- every op rounded once, as the tensor expressions of sample_ray
-//   cumdist   dist_k = |p_k - p_(k-1)|; the sequential scan with reset of k4_cumdist_thres, run wave-uniformly over the 64 lanes in step
-//             order with the carry held across chunks: every decision is the sequential definition's (no prefix-sum rewrite)
-//   filters   keep = inner | cumdist; mask_cache (k4s_maskcache); density (k4s_grid_corners / blend) -> raw2alpha (k4s_raw2alpha) ->
-//             alpha > thres; the exact transmittance product of k_alpha2weight incl. the T < 1e-3 stop; w > thres
-//   shading   survivors are queued in LDS (step, w) and shaded 64 at a time, lane = survivor: k0 trilinear (channel-major grid),
-//             features [k0 | viewdirs | sin | cos] (lib/dcvgo.py:334-340), the Linear-ReLU rgbnet as fp32 FMA chains, sigmoid;
-//             sum w rgb, sum w s_tab[k] (depth), alphainv_last = T, rgb += T bg.
-// The arithmetic of every stage is the staged kernels' (shared k4s_* helpers), so fused and staged paths agree to the order of the final sums.
-struct K4ContractedArgs {
-    const float *ro, *rd, *vd; int64_t n_rays;
-    const float *t_tab, *s_tab; int n_max;
-    float cx, cy, cz, rx, ry, rz, bg_len, dist_thres; int norm_l2;
-    const float* density; const float* k0; int C, X, Y, Z; const float *mn, *mx;
-    const uint8_t* mask; int MX, MY, MZ; const float *sc, *sh;
-    float act_shift, interval, thres, bg;
-    const float *w1, *b1, *w2, *b2, *w3, *b3; int dim0, n_hidden; const float* viewfreq; int n_pe;
-    float *rgb, *depth, *ainv; unsigned long long* counters;
-};
-
-__device__ __forceinline__ void k4c_point(const K4ContractedArgs& A, const float (&o)[3], const float (&d)[3], int k, float (&p)[3], bool& inner) {
-    const float t = A.t_tab[k];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = __fadd_rn(o[a], __fmul_rn(d[a], t));
-    float n;
-    if (A.norm_l2) n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(p[0], p[0]), __fmul_rn(p[1], p[1])), __fmul_rn(p[2], p[2])));
-    else n = fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]));
-    inner = n <= 1.f;
-    if (!inner) {
-        const float f = __fsub_rn(__fadd_rn(1.f, A.bg_len), __fmul_rn(__frcp_rn(n), A.bg_len));
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fdiv_rn(p[a], n), f);
-    }
+// ---------------------------------------------------------------- the one-launch marchers: k4_march_contracted_fwd, k4_march_vq_fwd, k4_march_bivox_fwd
+// Inference of DirectContractedVoxGO, DirectQVGO and DirectBiVoxGO in ONE launch per call.  The staged forwards materialise per-sample tables and
+// filter them up to three times with host synchronisations; here one WAVE walks one ray, lanes = 64 consecutive steps in depth order, and nothing
+// per sample leaves the chip.  The walk is k4w_walk (k4_ray_walk.h) for all three: filters, the exact transmittance product of k_alpha2weight incl.
+// the T < 1e-3 stop, the LDS survivor queue shaded 64 at a time, the per-ray sums.  A kernel supplies its ray setup, where a step's point comes from,
+// its pre-filter, its alpha, its shading and its epilogue.  The arithmetic of every stage is the staged kernels' (shared k4s_* helpers), so fused and
+// staged paths agree to the order of the final sums.
+static bool k4_grid_fill(K4Grid& G, const float* density, const float* k0, bool has_k0, int k0_ch, const int32_t (&dims)[3], const float* mn, const float* mx,
+                         const uint8_t* mask, const int32_t (&mdims)[3], const float* sc, const float* sh) {
+    G = K4Grid{density, k0, k0_ch, dims[0], dims[1], dims[2], mn, mx, mask, mdims[0], mdims[1], mdims[2], sc, sh};
+    return density && (k0 || !has_k0) && mn && mx && mask && sc && sh && dims[0] > 0 && dims[1] > 0 && dims[2] > 0 && mdims[0] > 0 && mdims[1] > 0 && mdims[2] > 0;
+}
+// An rgbnet of width 32 | 64 | 128 (width 0, no rgbnet, is the caller's case) -> K4_OK or the code of the first failing check.  The entry points differ
+// in what they have always answered: an unknown width's K4_ERR_UNSUPPORTED comes before the argument checks or, `width_last`, behind them; a bad
+// n_hidden is `hidden_err`.
+static int k4_net_fill(K4Net& N, int width, bool width_last, int n_hidden, int hidden_err, int dim0, int want_dim0, const float* freq, int n_pe,
+                       const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3) {
+    const bool width_ok = width == 32 || width == 64 || width == 128;
+    if (!width_ok && !width_last) return K4_ERR_UNSUPPORTED;
+    if (n_hidden != 0 && n_hidden != 1) return hidden_err;
+    REQ(n_pe >= 0 && dim0 == want_dim0 && (n_pe == 0 || freq));
+    REQ(w1 && b1 && w3 && b3 && (n_hidden == 0 || (w2 && b2)));
+    if (!width_ok) return K4_ERR_UNSUPPORTED;
+    N = K4Net{w1, b1, w2, b2, w3, b3, dim0, n_hidden, freq, n_pe};
+    return K4_OK;
 }
 
-// The Linear-ReLU rgbnet of a shaded sample as fp32 FMA chains + sigmoid, shared by the one-launch marchers.  The first layer's inputs come in order:
-// `pre(h)` adds the leading i0 inputs a caller holds in registers (none: a no-op), in(i) yields input i for i0 <= i < nin.
+// The Linear-ReLU rgbnet of a shaded sample as fp32 FMA chains + sigmoid.  The first layer's inputs come in order: `pre(h)` adds the leading i0 inputs a
+// caller holds in registers (none: a no-op), in(i) yields input i for i0 <= i < nin.
 template <int WIDTH, class PRE, class IN>
 __device__ __forceinline__ void k4c_mlp(const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
                                         const float* __restrict__ w3, const float* __restrict__ b3, int dim0, int n_hidden, int i0, int nin,
@@ -1165,163 +1154,119 @@ __device__ __forceinline__ void k4c_mlp(const float* __restrict__ w1, const floa
     for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-out[c]));
 }
 
+// k0 trilinear (channel-major grid), features [k0 | viewdirs | sin | cos] (lib/dcvgo.py:334-340), the rgbnet; WIDTH 0: sigmoid(k0)
 template <int WIDTH>
-__device__ __forceinline__ void k4c_shade(const K4ContractedArgs& A, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
+__device__ __forceinline__ void k4c_shade(const K4Grid& G, const K4Net& N, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
     size_t idx[8]; float w[8];
-    k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
-    const size_t plane = (size_t)A.X * A.Y * A.Z;
+    k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, G.X, G.Y, G.Z, idx, w);
+    const size_t plane = (size_t)G.X * G.Y * G.Z;
     if constexpr (WIDTH == 0) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-k4s_grid_blend(A.k0 + plane * c, idx, w)));
+        for (int c = 0; c < 3; ++c) rgb[c] = 1.f / (1.f + expf(-k4s_grid_blend(G.k0 + plane * c, idx, w)));
     } else {
-        const int P = A.n_pe;
-        k4c_mlp<WIDTH>(A.w1, A.b1, A.w2, A.b2, A.w3, A.b3, A.dim0, A.n_hidden, 0, A.C + 3 + 6 * P, [](float (&)[WIDTH]) {}, [&](int i) -> float {
-            if (i < A.C) return k4s_grid_blend(A.k0 + plane * i, idx, w);
-            const int e = i - A.C;
+        const int P = N.n_pe;
+        k4c_mlp<WIDTH>(N.w1, N.b1, N.w2, N.b2, N.w3, N.b3, N.dim0, N.n_hidden, 0, G.C + 3 + 6 * P, [](float (&)[WIDTH]) {}, [&](int i) -> float {
+            if (i < G.C) return k4s_grid_blend(G.k0 + plane * i, idx, w);
+            const int e = i - G.C;
             if (e < 3) return vd[e];
             const int q = e - 3, sc = q / (3 * P), r = q - sc * 3 * P, dd = r / P, f = r - dd * P;
-            const float v = __fmul_rn(vd[dd], A.viewfreq[f]);
+            const float v = __fmul_rn(vd[dd], N.freq[f]);
             return sc == 0 ? sinf(v) : cosf(v);
         }, rgb);
+    }
+}
+// density (k4s_grid_corners / blend) -> raw2alpha (k4s_raw2alpha)
+__device__ __forceinline__ float k4c_alpha(const K4Grid& G, const float (&p)[3], float act_shift, float interval) {
+    size_t idx[8]; float w[8];
+    k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, G.X, G.Y, G.Z, idx, w);
+    float e, alpha;
+    k4s_raw2alpha(k4s_grid_blend(G.density, idx, w), act_shift, interval, e, alpha);
+    return alpha;
+}
+
+// ---------------------------------------------------------------- DirectContractedVoxGO (lib/dcvgo.py)
+//   point     p_k = o' + d' t_tab[k] (k4w_unit_ray); norm (inf | l2); outside the unit ball p <- p / n ((1 + bg) - n^-1 bg)
+//             (torch's `bg_len / norm` is reciprocal * bg_len) -- every op rounded once, as the tensor expressions of sample_ray
+//   pre       inner | cumdist: dist_k = |p_k - p_(k-1)|; the sequential scan with reset of k4_cumdist_thres, run wave-uniformly over the 64 lanes in
+//             step order with the carry held across chunks: every decision is the sequential definition's (no prefix-sum rewrite)
+//   depth     sum w s_tab[k];  epilogue: alphainv_last = T, rgb += T bg
+struct K4ContractedArgs {
+    const float *ro, *rd, *vd; int64_t n_rays;
+    const float *t_tab, *s_tab; int n_max;
+    float cx, cy, cz, rx, ry, rz, bg_len, dist_thres; int norm_l2;
+    K4Grid G; K4Net N;
+    float act_shift, interval, thres, bg;
+    float *rgb, *depth, *ainv; unsigned long long* counters;
+};
+
+__device__ __forceinline__ void k4c_point(const K4ContractedArgs& A, const float (&o)[3], const float (&d)[3], int k, float (&p)[3], bool& inner) {
+    const float t = A.t_tab[k];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = __fadd_rn(o[a], __fmul_rn(d[a], t));
+    float n;
+    if (A.norm_l2) n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(p[0], p[0]), __fmul_rn(p[1], p[1])), __fmul_rn(p[2], p[2])));
+    else n = fmaxf(fmaxf(fabsf(p[0]), fabsf(p[1])), fabsf(p[2]));
+    inner = n <= 1.f;
+    if (!inner) {
+        const float f = __fsub_rn(__fadd_rn(1.f, A.bg_len), __fmul_rn(__frcp_rn(n), A.bg_len));
+#pragma unroll
+        for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fdiv_rn(p[a], n), f);
     }
 }
 
 template <int WIDTH>
 __global__ __launch_bounds__(64) void k_march_contracted(const K4ContractedArgs A) {
-    __shared__ int qk[128];
-    __shared__ float qw[128];
     const int64_t ray = blockIdx.x;
     if (ray >= A.n_rays) return;
     const int lane = k4_lane();
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    float o[3], d[3], vd[3];
-    {
-        const float dx = A.rd[ray * 3 + 0], dy = A.rd[ray * 3 + 1], dz = A.rd[ray * 3 + 2];
-        const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        const float c[3] = {A.cx, A.cy, A.cz}, r[3] = {A.rx, A.ry, A.rz}, dv[3] = {dx, dy, dz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            o[a] = __fdiv_rn(__fsub_rn(A.ro[ray * 3 + a], c[a]), r[a]);
-            d[a] = __fdiv_rn(dv[a], dn);
-            vd[a] = A.vd[ray * 3 + a];
-        }
-    }
-    const bool count = A.counters != nullptr;
-    float T = 1.f, cum = 0.f;
-    bool stopped = false;
-    int nq = 0;
-    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
-    unsigned long long c_pre = 0, c_mask = 0, c_alpha = 0, c_shade = 0;
-    auto shade_queue = [&](int n) {
-        if (lane < n) {
-            const int k = qk[lane];
-            const float wk = qw[lane];
+    float o[3], d[3];
+    k4w_unit_ray(A.ro, A.rd, ray, {A.cx, A.cy, A.cz}, {A.rx, A.ry, A.rz}, o, d);
+    const float vd[3] = {A.vd[ray * 3 + 0], A.vd[ray * 3 + 1], A.vd[ray * 3 + 2]};
+    float cum = 0.f;
+    const auto M = k4w_parts(A.n_max,
+        [&](int k, bool valid, float (&p)[3]) -> bool {
+            float q[3] = {0.f, 0.f, 0.f};
+            p[0] = p[1] = p[2] = 0.f;
+            bool inner = false, in_prev = false;
+            float dist = 0.f;
+            if (valid) {
+                k4c_point(A, o, d, k, p, inner);
+                if (k > 0) {
+                    k4c_point(A, o, d, k - 1, q, in_prev);
+                    const float ex = __fsub_rn(p[0], q[0]), ey = __fsub_rn(p[1], q[1]), ez = __fsub_rn(p[2], q[2]);
+                    dist = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)));
+                }
+            }
+            // the cumdist scan: wave-uniform carry, steps in order (k4_cumdist_thres's chain on dist[k - 1] = |p_k - p_(k-1)|)
+            bool over_me = false;
+            const int base = k - lane, lim = min(64, A.n_max - base);
+            for (int l = 0; l < lim; ++l) {
+                if (base + l == 0) continue;
+                cum = __fadd_rn(cum, k4_readlane(dist, l));
+                const bool over = cum > A.dist_thres;
+                cum = __fmul_rn(cum, (float)(!over));
+                if (lane == l) over_me = over;
+            }
+            return valid && (inner || over_me);
+        },
+        [&](const float (&p)[3]) { return k4s_maskcache(A.G.mask, p[0], p[1], p[2], A.G.sc, A.G.sh, A.G.MX, A.G.MY, A.G.MZ) != 0; },
+        [&](const float (&p)[3]) { return k4c_alpha(A.G, p, A.act_shift, A.interval); },
+        [&](int k, float (&rgb)[3]) {
             float p[3]; bool in;
             k4c_point(A, o, d, k, p, in);
-            float rgb[3];
-            k4c_shade<WIDTH>(A, p, vd, rgb);
-            acc_r = fmaf(wk, rgb[0], acc_r);
-            acc_g = fmaf(wk, rgb[1], acc_g);
-            acc_b = fmaf(wk, rgb[2], acc_b);
-            acc_d = fmaf(wk, A.s_tab[k], acc_d);
-        }
-    };
-    for (int base = 0; base < A.n_max; base += 64) {
-        if (stopped && !count) break;
-        const int k = base + lane;
-        const bool valid = k < A.n_max;
-        float p[3] = {0.f, 0.f, 0.f}, q[3] = {0.f, 0.f, 0.f};
-        bool inner = false, in_prev = false;
-        float dist = 0.f;
-        if (valid) {
-            k4c_point(A, o, d, k, p, inner);
-            if (k > 0) {
-                k4c_point(A, o, d, k - 1, q, in_prev);
-                const float ex = __fsub_rn(p[0], q[0]), ey = __fsub_rn(p[1], q[1]), ez = __fsub_rn(p[2], q[2]);
-                dist = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)));
-            }
-        }
-        // the cumdist scan: wave-uniform carry, steps in order (k4_cumdist_thres's chain on dist[k - 1] = |p_k - p_(k-1)|)
-        bool over_me = false;
-        const int lim = min(64, A.n_max - base);
-        for (int l = 0; l < lim; ++l) {
-            if (base + l == 0) continue;
-            cum = __fadd_rn(cum, k4_readlane(dist, l));
-            const bool over = cum > A.dist_thres;
-            cum = __fmul_rn(cum, (float)(!over));
-            if (lane == l) over_me = over;
-        }
-        bool keep = valid && (inner || over_me);
-        if (keep) keep = k4s_maskcache(A.mask, p[0], p[1], p[2], A.sc, A.sh, A.MX, A.MY, A.MZ) != 0;
-        const bool pre = valid && (inner || over_me);
-        float alpha = 0.f;
-        if (keep) {
-            size_t idx[8]; float w[8];
-            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
-            float e;
-            k4s_raw2alpha(k4s_grid_blend(A.density, idx, w), A.act_shift, A.interval, e, alpha);
-        }
-        const bool apass = keep && (A.thres > 0.f ? alpha > A.thres : true);
-        // transmittance: the exact sequential product of k_alpha2weight over the alpha-passing samples in step order
-        float myw = 0.f;
-        bool wpass = false;
-        uint64_t bm = __ballot(apass);
-        while (bm && !stopped) {
-            const int l = __builtin_ctzll(bm);
-            const float al = k4_readlane(alpha, l);
-            if (lane == l) myw = T * al;
-            T = fmaf(-T, al, T);
-            bm &= bm - 1;
-            if (T < 1e-3f) stopped = true;
-            if (lane == l) wpass = A.thres > 0.f ? myw > A.thres : true;
-        }
-        if (count) {
-            c_pre += __popcll(__ballot(pre));
-            c_mask += __popcll(__ballot(keep));
-            c_alpha += __popcll(__ballot(apass));
-        }
-        const uint64_t sm = __ballot(wpass);
-        const int ns = __popcll(sm);
-        c_shade += ns;
-        if (wpass) {
-            const int slot = nq + __popcll(sm & below);
-            qk[slot] = k;
-            qw[slot] = myw;
-        }
-        nq += ns;
-        __syncthreads();
-        if (nq >= 64) {
-            shade_queue(64);
-            __syncthreads();
-            int rest = nq - 64, mk = 0; float mw = 0.f;
-            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
-            __syncthreads();
-            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
-            __syncthreads();
-            nq = rest;
-        }
-    }
-    shade_queue(nq);
-    // per-ray sums: wave reduction in a fixed lane order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_r += __shfl_down(acc_r, off);
-        acc_g += __shfl_down(acc_g, off);
-        acc_b += __shfl_down(acc_b, off);
-        acc_d += __shfl_down(acc_d, off);
-    }
+            k4c_shade<WIDTH>(A.G, A.N, p, vd, rgb);
+        },
+        [&](int k) { return A.s_tab[k]; });
+    const K4WalkOut R = k4w_walk<true, false>(M, lane, A.thres, A.counters != nullptr);
     if (lane == 0) {
-        A.rgb[ray * 3 + 0] = fmaf(T, A.bg, acc_r);
-        A.rgb[ray * 3 + 1] = fmaf(T, A.bg, acc_g);
-        A.rgb[ray * 3 + 2] = fmaf(T, A.bg, acc_b);
-        A.depth[ray] = acc_d;
-        A.ainv[ray] = T;
-        if (count) {
-            if (!(A.thres > 0.f)) c_shade = c_alpha;          // no weight filter: every alpha sample is shaded (w = 0 behind the stop)
-            atomicAdd(&A.counters[0], c_pre);
-            atomicAdd(&A.counters[1], c_mask);
-            atomicAdd(&A.counters[2], c_alpha);
-            atomicAdd(&A.counters[3], c_shade);
+        A.rgb[ray * 3 + 0] = fmaf(R.T, A.bg, R.sum[0]);
+        A.rgb[ray * 3 + 1] = fmaf(R.T, A.bg, R.sum[1]);
+        A.rgb[ray * 3 + 2] = fmaf(R.T, A.bg, R.sum[2]);
+        A.depth[ray] = R.sum[3];
+        A.ainv[ray] = R.T;
+        if (A.counters != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) atomicAdd(&A.counters[i], R.cnt[i]);
         }
     }
 }
@@ -1329,29 +1274,23 @@ __global__ __launch_bounds__(64) void k_march_contracted(const K4ContractedArgs 
 extern "C" int k4_march_contracted_fwd(const k4_contracted_desc* g, void* stream) {
     REQ(g && g->n_rays >= 0 && g->n_max > 0);
     if (g->n_rays == 0) return K4_OK;
-    REQ(g->rays_o && g->rays_d && g->viewdirs && g->t_tab && g->s_tab && g->density && g->k0 && g->mask && g->xyz_min && g->xyz_max);
-    REQ(g->xyz2ijk_scale && g->xyz2ijk_shift && g->rgb && g->depth && g->alphainv_last);
-    REQ(g->dims[0] > 0 && g->dims[1] > 0 && g->dims[2] > 0 && g->mask_dims[0] > 0 && g->mask_dims[1] > 0 && g->mask_dims[2] > 0);
+    K4ContractedArgs A;
+    REQ(g->rays_o && g->rays_d && g->viewdirs && g->t_tab && g->s_tab && g->rgb && g->depth && g->alphainv_last);
+    REQ(k4_grid_fill(A.G, g->density, g->k0, true, g->k0_ch, g->dims, g->xyz_min, g->xyz_max, g->mask, g->mask_dims, g->xyz2ijk_scale, g->xyz2ijk_shift));
     const int W = g->width;
+    A.N = K4Net{};
     if (W == 0) { REQ(g->k0_ch == 3); }
     else {
-        if (W != 32 && W != 64 && W != 128) return K4_ERR_UNSUPPORTED;
-        REQ(g->n_hidden == 0 || g->n_hidden == 1);
-        REQ(g->n_pe >= 0 && g->dim0 == g->k0_ch + 3 + 6 * g->n_pe && (g->n_pe == 0 || g->viewfreq));
-        REQ(g->w1 && g->b1 && g->w3 && g->b3 && (g->n_hidden == 0 || (g->w2 && g->b2)));
+        const int rc = k4_net_fill(A.N, W, false, g->n_hidden, K4_ERR_BAD_ARG, g->dim0, g->k0_ch + 3 + 6 * g->n_pe, g->viewfreq, g->n_pe,
+                                   g->w1, g->b1, g->w2, g->b2, g->w3, g->b3);
+        if (rc) return rc;
     }
-    K4ContractedArgs A;
     A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays;
     A.t_tab = g->t_tab; A.s_tab = g->s_tab; A.n_max = g->n_max;
     A.cx = g->scene_center[0]; A.cy = g->scene_center[1]; A.cz = g->scene_center[2];
     A.rx = g->scene_radius[0]; A.ry = g->scene_radius[1]; A.rz = g->scene_radius[2];
     A.bg_len = g->bg_len; A.dist_thres = g->dist_thres; A.norm_l2 = g->norm_l2;
-    A.density = g->density; A.k0 = g->k0; A.C = g->k0_ch; A.X = g->dims[0]; A.Y = g->dims[1]; A.Z = g->dims[2];
-    A.mn = g->xyz_min; A.mx = g->xyz_max;
-    A.mask = g->mask; A.MX = g->mask_dims[0]; A.MY = g->mask_dims[1]; A.MZ = g->mask_dims[2]; A.sc = g->xyz2ijk_scale; A.sh = g->xyz2ijk_shift;
     A.act_shift = g->act_shift; A.interval = g->interval; A.thres = g->fast_color_thres; A.bg = g->bg;
-    A.w1 = g->w1; A.b1 = g->b1; A.w2 = g->w2; A.b2 = g->b2; A.w3 = g->w3; A.b3 = g->b3; A.dim0 = g->dim0; A.n_hidden = g->n_hidden;
-    A.viewfreq = g->viewfreq; A.n_pe = g->n_pe;
     A.rgb = g->rgb; A.depth = g->depth; A.ainv = g->alphainv_last; A.counters = (unsigned long long*)g->counters;
     const dim3 grid((unsigned)g->n_rays), block(64);
     switch (W) {
@@ -1362,39 +1301,37 @@ extern "C" int k4_march_contracted_fwd(const k4_contracted_desc* g, void* stream
     }
     return k4_check_launch();
 }
-// ---------------------------------------------------------------- DirectQVGO inference: ONE launch per call (k4_march_vq_fwd)
-// DirectMPIGO's geometry with a codebook colour feature (lib/dvqgo.py:279-408 under torch.no_grad, module in eval mode).  One wave walks one ray, lanes = 64
-// consecutive samples, in depth order, as k_march_contracted does:
-//   geometry  the three filters of k_train_select_mpi, expression for expression (NDC point, bounding box, mask cache, density + act_shift grid,
-//             raw2alpha with shift 0, alpha > thres, the sequential transmittance product with the T < 1e-3 stop, weight > thres)
-//   shading   survivors are queued in LDS (step, w) and shaded 64 at a time, lane = survivor: the positional embedding (k_rgbnet_input_mpi's
-//             arithmetic), the two-layer projection, the codeword search over the prepared codebook and v + (e - v) (k4_vq.h: the expressions of the
-//             staged lookup, so the chosen codeword is its choice), the rgbnet on [vq_emb | pe_emb | viewdirs] (k4c_mlp), sigmoid;
-//             sum w rgb, sum w (step + 0.5) / n_samples (depth), alphainv_last = T, rgb += T bg.  Nothing per sample is written to memory.
+// ---------------------------------------------------------------- DirectQVGO (lib/dvqgo.py:279-408 under torch.no_grad, module in eval mode)
+// DirectMPIGO's geometry with a codebook colour feature:
+//   point     the NDC point of k_train_select_mpi (k4s_ndc_point);  pre: inside the bounding box
+//   alpha     density + act_shift grid, raw2alpha with shift 0 -- the filters of k_train_select_mpi, expression for expression
+//   shading   the positional embedding (k_rgbnet_input_mpi's arithmetic), the two-layer projection, the codeword search over the prepared codebook and
+//             v + (e - v) (k4_vq.h: the expressions of the staged lookup, so the chosen codeword is its choice), the rgbnet on
+//             [vq_emb | pe_emb | viewdirs] (k4c_mlp), sigmoid
+//   depth     sum w (step + 0.5) / n_samples;  epilogue: alphainv_last = T, rgb += T bg.  No counters.
 struct K4VqArgs {
     const float *ro, *rd, *vd; int64_t n_rays; int n_samples;
-    const float* density; int X, Y, Z; const float* act; int AD; const float *mn, *mx;
-    const uint8_t* mask; int MX, MY, MZ; const float *sc, *sh;
+    K4Grid G; const float* act; int AD;                      // (G.k0 / G.C unset: the colour feature is the codebook's)
     float interval, thres, bg;
-    const float* posfreq; int n_pe;
     const float *pw1, *pb1, *pw2, *pb2; int dim; const float* codebook; int n_embed;
-    const float *w1, *b1, *w2, *b2, *w3, *b3; int dim0, n_hidden;
+    K4Net N;                                                 // (N.freq / N.n_pe: the positional embedding's)
     float *rgb, *depth, *ainv;
 };
 
 template <int WIDTH, int MAXD>
 __device__ __forceinline__ void k4v_shade(const K4VqArgs& A, const float (&p)[3], const float (&vd)[3], float (&rgb)[3]) {
-    const int P = A.n_pe, npe = 3 + 6 * P;
+    const K4Net& N = A.N;
+    const int P = N.n_pe, npe = 3 + 6 * P;
     float spa[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {                                                           // pe_spa, lib/dvqgo.py:322: sub, div, flip, mul, sub
         const int a = 2 - j;
-        spa[j] = __fsub_rn(__fmul_rn(__fdiv_rn(__fsub_rn(p[a], A.mn[a]), __fsub_rn(A.mx[a], A.mn[a])), 2.f), 1.f);
+        spa[j] = __fsub_rn(__fmul_rn(__fdiv_rn(__fsub_rn(p[a], A.G.mn[a]), __fsub_rn(A.G.mx[a], A.G.mn[a])), 2.f), 1.f);
     }
     auto pe = [&](int col) -> float {                                                       // pe_emb column (k_rgbnet_input_mpi)
         if (col < 3) return col == 0 ? spa[0] : col == 1 ? spa[1] : spa[2];
         const int c2 = col - 3, which = c2 / (3 * P), r = c2 - which * 3 * P, d = r / P, f = r - d * P;
-        const float arg = __fmul_rn(d == 0 ? spa[0] : d == 1 ? spa[1] : spa[2], A.posfreq[f]);
+        const float arg = __fmul_rn(d == 0 ? spa[0] : d == 1 ? spa[1] : spa[2], N.freq[f]);
         return which == 0 ? sinf(arg) : cosf(arg);
     };
     float h[MAXD], v[MAXD];
@@ -1407,12 +1344,12 @@ __device__ __forceinline__ void k4v_shade(const K4VqArgs& A, const float (&p)[3]
 #pragma unroll
     for (int j = 0; j < MAXD; ++j)
         if (j < A.dim) v[j] = __fadd_rn(v[j], __fsub_rn(row[j], v[j]));                      // vq_input + (quantize - vq_input), lib/grid.py:96
-    k4c_mlp<WIDTH>(A.w1, A.b1, A.w2, A.b2, A.w3, A.b3, A.dim0, A.n_hidden, A.dim, A.dim + npe + 3, [&](float (&hh)[WIDTH]) {
+    k4c_mlp<WIDTH>(N.w1, N.b1, N.w2, N.b2, N.w3, N.b3, N.dim0, N.n_hidden, A.dim, A.dim + npe + 3, [&](float (&hh)[WIDTH]) {
 #pragma unroll
         for (int c = 0; c < MAXD; ++c)
             if (c < A.dim) {
 #pragma unroll
-                for (int j = 0; j < WIDTH; ++j) hh[j] = fmaf(A.w1[(size_t)j * A.dim0 + c], v[c], hh[j]);
+                for (int j = 0; j < WIDTH; ++j) hh[j] = fmaf(N.w1[(size_t)j * N.dim0 + c], v[c], hh[j]);
             }
     }, [&](int i) -> float {
         const int e = i - A.dim;
@@ -1423,126 +1360,66 @@ __device__ __forceinline__ void k4v_shade(const K4VqArgs& A, const float (&p)[3]
 
 template <int WIDTH, int MAXD>
 __global__ __launch_bounds__(64) void k_march_vq(const K4VqArgs A) {
-    __shared__ int qk[128];
-    __shared__ float qw[128];
     const int64_t ray = blockIdx.x;
     if (ray >= A.n_rays) return;
     const int lane = k4_lane();
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
     const float vd[3] = {A.vd[ray * 3 + 0], A.vd[ray * 3 + 1], A.vd[ray * 3 + 2]};
-    float T = 1.f;
-    bool stopped = false;
-    int nq = 0;
-    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
-    auto shade_queue = [&](int n) {
-        if (lane < n) {
-            const int k = qk[lane];
-            const float wk = qw[lane];
-            float p[3], rgb[3];
-            k4s_ndc_point(A.ro, A.rd, ray, k, A.n_samples, p);
-            k4v_shade<WIDTH, MAXD>(A, p, vd, rgb);
-            acc_r = fmaf(wk, rgb[0], acc_r);
-            acc_g = fmaf(wk, rgb[1], acc_g);
-            acc_b = fmaf(wk, rgb[2], acc_b);
-            acc_d = fmaf(wk, __fdiv_rn((float)k + 0.5f, (float)A.n_samples), acc_d);
-        }
-    };
-    for (int base = 0; base < A.n_samples && !stopped; base += 64) {
-        const int k = base + lane;
-        const bool valid = k < A.n_samples;
-        float p[3];
-        k4s_ndc_point(A.ro, A.rd, ray, valid ? k : 0, A.n_samples, p);
-        bool f2 = valid && !k4s_outbbox(p, A.mn, A.mx);
-        if (f2) f2 = k4s_maskcache(A.mask, p[0], p[1], p[2], A.sc, A.sh, A.MX, A.MY, A.MZ) != 0;
-        float alpha = 0.f;
-        if (f2) {
+    const K4Grid& G = A.G;
+    const auto M = k4w_parts(A.n_samples,
+        [&](int k, bool valid, float (&p)[3]) -> bool {
+            k4s_ndc_point(A.ro, A.rd, ray, valid ? k : 0, A.n_samples, p);
+            return valid && !k4s_outbbox(p, G.mn, G.mx);
+        },
+        [&](const float (&p)[3]) { return k4s_maskcache(G.mask, p[0], p[1], p[2], G.sc, G.sh, G.MX, G.MY, G.MZ) != 0; },
+        [&](const float (&p)[3]) {
             size_t idx[8]; float w[8];
-            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, A.X, A.Y, A.Z, idx, w);
-            const float den = k4s_grid_blend(A.density, idx, w);
-            k4s_grid_corners(p[0], p[1], p[2], A.mn, A.mx, 1, 1, A.AD, idx, w);
+            k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, G.X, G.Y, G.Z, idx, w);
+            const float den = k4s_grid_blend(G.density, idx, w);
+            k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, 1, 1, A.AD, idx, w);
             const float ash = k4s_grid_blend(A.act, idx, w);
             const float sum = den + ash;
-            float e;
+            float e, alpha;
             k4s_raw2alpha(sum, 0.f, A.interval, e, alpha);
-            f2 = A.thres > 0.f ? alpha > A.thres : true;
-        }
-        float myw = 0.f;
-        bool hit = false;                                         // this lane's sample entered the transmittance product
-        uint64_t bm = __ballot(f2);
-        while (bm && !stopped) {
-            const int l = __builtin_ctzll(bm);
-            const float al = k4_readlane(alpha, l);
-            if (lane == l) { myw = T * al; hit = true; }
-            T = fmaf(-T, al, T);
-            bm &= bm - 1;
-            if (T < 1e-3f) stopped = true;
-        }
-        // weight > thres; without a threshold every alpha sample is shaded, those behind the stop with weight 0 (they add nothing: not queued)
-        const bool wpass = A.thres > 0.f ? (f2 && myw > A.thres) : hit;
-        const uint64_t sm = __ballot(wpass);
-        const int ns = __popcll(sm);
-        if (wpass) {
-            const int slot = nq + __popcll(sm & below);
-            qk[slot] = k;
-            qw[slot] = myw;
-        }
-        nq += ns;
-        __syncthreads();
-        if (nq >= 64) {
-            shade_queue(64);
-            __syncthreads();
-            int rest = nq - 64, mk = 0; float mw = 0.f;
-            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
-            __syncthreads();
-            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
-            __syncthreads();
-            nq = rest;
-        }
-    }
-    shade_queue(nq);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_r += __shfl_down(acc_r, off);
-        acc_g += __shfl_down(acc_g, off);
-        acc_b += __shfl_down(acc_b, off);
-        acc_d += __shfl_down(acc_d, off);
-    }
+            return alpha;
+        },
+        [&](int k, float (&rgb)[3]) {
+            float p[3];
+            k4s_ndc_point(A.ro, A.rd, ray, k, A.n_samples, p);
+            k4v_shade<WIDTH, MAXD>(A, p, vd, rgb);
+        },
+        [n = A.n_samples](int k) { return __fdiv_rn((float)k + 0.5f, (float)n); });
+    const K4WalkOut R = k4w_walk<false, false>(M, lane, A.thres, false);
     if (lane == 0) {
-        A.rgb[ray * 3 + 0] = fmaf(T, A.bg, acc_r);
-        A.rgb[ray * 3 + 1] = fmaf(T, A.bg, acc_g);
-        A.rgb[ray * 3 + 2] = fmaf(T, A.bg, acc_b);
-        A.depth[ray] = acc_d;
-        A.ainv[ray] = T;
+        A.rgb[ray * 3 + 0] = fmaf(R.T, A.bg, R.sum[0]);
+        A.rgb[ray * 3 + 1] = fmaf(R.T, A.bg, R.sum[1]);
+        A.rgb[ray * 3 + 2] = fmaf(R.T, A.bg, R.sum[2]);
+        A.depth[ray] = R.sum[3];
+        A.ainv[ray] = R.T;
     }
 }
 
 extern "C" int k4_march_vq_fwd(const k4_vq_desc* g, void* stream) {
     REQ(g && g->n_rays >= 0 && g->n_samples > 1);
     if (g->n_rays == 0) return K4_OK;
-    REQ(g->rays_o && g->rays_d && g->viewdirs && g->density && g->act_shift && g->mask && g->xyz_min && g->xyz_max && g->xyz2ijk_scale && g->xyz2ijk_shift);
-    REQ(g->rgb && g->depth && g->alphainv_last);
-    REQ(g->dims[0] > 0 && g->dims[1] > 0 && g->dims[2] > 0 && g->act_depth > 0 && g->mask_dims[0] > 0 && g->mask_dims[1] > 0 && g->mask_dims[2] > 0);
-    REQ(g->n_pe >= 0 && g->n_pe <= 10 && (g->n_pe == 0 || g->posfreq) && g->dim >= 1 && g->dim <= VQ_MAXD && g->n_embed >= 1 && g->codebook);
-    REQ(g->pw1 && g->pb1 && g->pw2 && g->pb2 && g->w1 && g->b1 && g->w3 && g->b3);
-    REQ((g->n_hidden == 0 || g->n_hidden == 1) && (g->n_hidden == 0 || (g->w2 && g->b2)) && g->dim0 == g->dim + 3 + 6 * g->n_pe + 3);
-    if (g->n_rays > 0x7fffffffLL) return K4_ERR_UNSUPPORTED;
-    const int W = g->width;
-    if (W != 32 && W != 64 && W != 128) return K4_ERR_UNSUPPORTED;
     K4VqArgs A;
+    REQ(g->rays_o && g->rays_d && g->viewdirs && g->act_shift && g->act_depth > 0 && g->rgb && g->depth && g->alphainv_last);
+    REQ(k4_grid_fill(A.G, g->density, nullptr, false, 0, g->dims, g->xyz_min, g->xyz_max, g->mask, g->mask_dims, g->xyz2ijk_scale, g->xyz2ijk_shift));
+    REQ(g->n_pe <= 10 && g->dim >= 1 && g->dim <= VQ_MAXD && g->n_embed >= 1 && g->codebook && g->pw1 && g->pb1 && g->pw2 && g->pb2);
+    const int rc = k4_net_fill(A.N, g->width, true, g->n_hidden, K4_ERR_BAD_ARG, g->dim0, g->dim + 3 + 6 * g->n_pe + 3, g->posfreq, g->n_pe,
+                               g->w1, g->b1, g->w2, g->b2, g->w3, g->b3);
+    if (rc) return rc;
+    if (g->n_rays > 0x7fffffffLL) return K4_ERR_UNSUPPORTED;
     A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays; A.n_samples = g->n_samples;
-    A.density = g->density; A.X = g->dims[0]; A.Y = g->dims[1]; A.Z = g->dims[2]; A.act = g->act_shift; A.AD = g->act_depth; A.mn = g->xyz_min; A.mx = g->xyz_max;
-    A.mask = g->mask; A.MX = g->mask_dims[0]; A.MY = g->mask_dims[1]; A.MZ = g->mask_dims[2]; A.sc = g->xyz2ijk_scale; A.sh = g->xyz2ijk_shift;
+    A.act = g->act_shift; A.AD = g->act_depth;
     A.interval = g->interval; A.thres = g->fast_color_thres; A.bg = g->bg;
-    A.posfreq = g->posfreq; A.n_pe = g->n_pe;
     A.pw1 = g->pw1; A.pb1 = g->pb1; A.pw2 = g->pw2; A.pb2 = g->pb2; A.dim = g->dim; A.codebook = g->codebook; A.n_embed = g->n_embed;
-    A.w1 = g->w1; A.b1 = g->b1; A.w2 = g->w2; A.b2 = g->b2; A.w3 = g->w3; A.b3 = g->b3; A.dim0 = g->dim0; A.n_hidden = g->n_hidden;
     A.rgb = g->rgb; A.depth = g->depth; A.ainv = g->alphainv_last;
     const dim3 grid((unsigned)g->n_rays), block(64);
     // register arrays sized for the codeword's channel count: 8 | 16 | 32 (the same guarded chains: the same bits)
 #define K4_VQ(WD) do { if (g->dim <= 8) hipLaunchKernelGGL((k_march_vq<WD, 8>), grid, block, 0, ST, A); \
                        else if (g->dim <= 16) hipLaunchKernelGGL((k_march_vq<WD, 16>), grid, block, 0, ST, A); \
                        else hipLaunchKernelGGL((k_march_vq<WD, 32>), grid, block, 0, ST, A); } while (0)
-    switch (W) {
+    switch (g->width) {
         case 32:  K4_VQ(32); break;
         case 64:  K4_VQ(64); break;
         default:  K4_VQ(128); break;
@@ -1587,35 +1464,25 @@ extern "C" int k4_sample_bg_pts_on_rays(const float* o, const float* d, const fl
     return k4_check_launch();
 }
 
-// ---------------------------------------------------------------- DirectBiVoxGO inference: ONE launch per call (k4_march_bivox_fwd)
-// The staged forward (lib/dbvgo.py) builds the foreground sample list (one host synchronisation for its length), an [N][N_outer][3] background table,
-// filters each up to three times (a synchronisation per filter) and sums per ray.  Here one WAVE walks one ray through both passes, lanes = 64
-// consecutive steps in depth order, in the shape of k_march_contracted above and on its helpers:
-//   foreground  o' = (o - c) / r, d' = d / |d| (each op rounded once, as the tensor expressions of sample_ray); aabb_t / n_steps_of / the start and
-//               direction of k_pts_fill; p_k = fma(dir, stepdist k, start); bbox test; mask_cache[0]; density[0] -> k4s_raw2alpha -> alpha > thres; the
-//               exact transmittance product of k_alpha2weight incl. the T < 1e-3 stop; w > thres; survivors queued in LDS and shaded 64 at a time
-//               (k4c_shade with grid 0's k0 / rgbnet)
-//   background  only when T_fg > thres: p_k = k4s_bg_point(o', d', t_max, k of n_outer); mask_cache[1]; density[1]; the same filters and product;
-//               k4c_shade with grid 1's k0 / rgbnet (WIDTH 0: sigmoid(k0))
-//   per pass    sum w rgb, sum w k, T, the last kept step (thres == 0: every in-mask sample is kept, also behind the stop -- lib/dbvgo.py:273,283)
-//   compose     lib/dbvgo.py:357-359,392-394, every op rounded once as the tensor expressions are.
-// Each grid's pointers travel in a K4ContractedArgs (the fields the lookups and k4c_shade read), so both passes run the contracted kernel's shading code.
+// ---------------------------------------------------------------- DirectBiVoxGO (lib/dbvgo.py): two walks per ray
+//   foreground  o', d' (k4w_unit_ray); aabb_t / n_steps_of / the start and direction of k_pts_fill; p_k = fma(dir, stepdist k, start);  pre: inside the
+//               bounding box;  grid 0's mask, density, k0 / rgbnet
+//   background  only when T_fg > thres: p_k = k4s_bg_point(o', d', t_max, k of n_outer);  no pre-filter;  grid 1's mask, density, k0 / rgbnet
+//               (WIDTH 0: sigmoid(k0))
+//   per pass    depth: sum w k;  the last kept step (thres == 0: every in-mask sample is kept, also behind the stop -- lib/dbvgo.py:273,283)
+//   epilogue    lib/dbvgo.py:357-359,392-394, every op rounded once as the tensor expressions are
 struct K4BivoxArgs {
-    K4ContractedArgs ph[2];
+    K4Grid G[2]; K4Net N[2];
     const float *ro, *rd, *vd; int64_t n_rays;
     float cx, cy, cz, rx, ry, rz, stepdist, far, bg_preserve; int n_outer;
     float act_shift, interval, thres, bg;
     float *rgb, *depth, *ainv_fg, *ainv_bg; unsigned long long* counters;
 };
+
 struct K4BivoxRay { float o[3], d[3], vd[3], start[3], dir[3], t_max; };
 
-// one pass of one ray: -> T, sum[0..2] = sum w rgb, sum[3] = sum w k (valid in lane 0), last = the last kept step or -1 (all lanes), cnt (wave-uniform)
 template <int WIDTH, bool BG>
-__device__ __forceinline__ void k4b_pass(const K4BivoxArgs& A, const K4ContractedArgs& G, const K4BivoxRay& R, int n_steps, int lane, int* qk, float* qw,
-                                         float& T_out, float (&sum)[4], int& last, unsigned long long (&cnt)[4]) {
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const bool count = A.counters != nullptr;
-    const bool filt = A.thres > 0.f;
+__device__ __forceinline__ K4WalkOut k4b_pass(const K4BivoxArgs& A, const K4Grid& G, const K4Net& N, const K4BivoxRay& R, int n_steps, int lane) {
     auto point = [&](int k, float (&p)[3]) {
         if (BG) k4s_bg_point(R.o, R.d, R.t_max, A.bg_preserve, k, A.n_outer, p);
         else {
@@ -1624,122 +1491,36 @@ __device__ __forceinline__ void k4b_pass(const K4BivoxArgs& A, const K4Contracte
             for (int a = 0; a < 3; ++a) p[a] = fmaf(R.dir[a], dist, R.start[a]);
         }
     };
-    float T = 1.f;
-    bool stopped = false;
-    int nq = 0, my_last = -1;
-    float acc_r = 0.f, acc_g = 0.f, acc_b = 0.f, acc_d = 0.f;
-    unsigned long long c_pre = 0, c_mask = 0, c_alpha = 0, c_shade = 0;
-    auto shade_queue = [&](int n) {
-        if (lane < n) {
-            const int k = qk[lane];
-            const float wk = qw[lane];
-            float p[3], rgb[3];
+    const auto M = k4w_parts(n_steps,
+        [&](int k, bool valid, float (&p)[3]) -> bool {
+            p[0] = p[1] = p[2] = 0.f;
+            if (!valid) return false;
             point(k, p);
-            k4c_shade<WIDTH>(G, p, R.vd, rgb);
-            acc_r = fmaf(wk, rgb[0], acc_r);
-            acc_g = fmaf(wk, rgb[1], acc_g);
-            acc_b = fmaf(wk, rgb[2], acc_b);
-            acc_d = fmaf(wk, (float)k, acc_d);
-        }
-    };
-    for (int base = 0; base < n_steps; base += 64) {
-        if (stopped && !count && filt) break;             // (thres == 0: the samples behind the stop are kept and move the last step)
-        const int k = base + lane;
-        float p[3] = {0.f, 0.f, 0.f};
-        bool pre = false;
-        if (k < n_steps) {
+            return BG ? true : !k4s_outbbox(p, G.mn, G.mx);
+        },
+        [&](const float (&p)[3]) { return k4s_maskcache(G.mask, p[0], p[1], p[2], G.sc, G.sh, G.MX, G.MY, G.MZ) != 0; },
+        [&](const float (&p)[3]) { return k4c_alpha(G, p, A.act_shift, A.interval); },
+        [&](int k, float (&rgb)[3]) {
+            float p[3];
             point(k, p);
-            pre = BG ? true : !k4s_outbbox(p, G.mn, G.mx);
-        }
-        bool keep = pre;
-        if (keep) keep = k4s_maskcache(G.mask, p[0], p[1], p[2], G.sc, G.sh, G.MX, G.MY, G.MZ) != 0;
-        float alpha = 0.f;
-        if (keep && (!stopped || count)) {
-            size_t idx[8]; float w[8];
-            k4s_grid_corners(p[0], p[1], p[2], G.mn, G.mx, G.X, G.Y, G.Z, idx, w);
-            float e;
-            k4s_raw2alpha(k4s_grid_blend(G.density, idx, w), A.act_shift, A.interval, e, alpha);
-        }
-        const bool apass = keep && (filt ? alpha > A.thres : true);
-        // transmittance: the exact sequential product of k_alpha2weight over the alpha-passing samples in step order
-        float myw = 0.f;
-        bool wpass = false;
-        uint64_t bm = __ballot(apass);
-        while (bm && !stopped) {
-            const int l = __builtin_ctzll(bm);
-            const float al = k4_readlane(alpha, l);
-            if (lane == l) myw = T * al;
-            T = fmaf(-T, al, T);
-            bm &= bm - 1;
-            if (T < 1e-3f) stopped = true;
-            if (lane == l) wpass = filt ? myw > A.thres : true;
-        }
-        if (count) {
-            c_pre += __popcll(__ballot(pre));
-            c_mask += __popcll(__ballot(keep));
-            c_alpha += __popcll(__ballot(apass));
-        }
-        if (filt ? wpass : keep) my_last = k;
-        const uint64_t sm = __ballot(wpass);
-        const int ns = __popcll(sm);
-        c_shade += ns;
-        if (wpass) {
-            const int slot = nq + __popcll(sm & below);
-            qk[slot] = k;
-            qw[slot] = myw;
-        }
-        nq += ns;
-        __syncthreads();
-        if (nq >= 64) {
-            shade_queue(64);
-            __syncthreads();
-            int rest = nq - 64, mk = 0; float mw = 0.f;
-            if (lane < rest) { mk = qk[64 + lane]; mw = qw[64 + lane]; }
-            __syncthreads();
-            if (lane < rest) { qk[lane] = mk; qw[lane] = mw; }
-            __syncthreads();
-            nq = rest;
-        }
-    }
-    shade_queue(nq);
-    __syncthreads();                                       // the next pass refills the queue
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        acc_r += __shfl_down(acc_r, off);
-        acc_g += __shfl_down(acc_g, off);
-        acc_b += __shfl_down(acc_b, off);
-        acc_d += __shfl_down(acc_d, off);
-        my_last = max(my_last, __shfl_xor(my_last, off));
-    }
-    T_out = T;
-    sum[0] = acc_r; sum[1] = acc_g; sum[2] = acc_b; sum[3] = acc_d;
-    last = my_last;
-    if (!filt) c_shade = c_alpha;                          // no weight filter: every alpha sample is shaded (w = 0 behind the stop)
-    cnt[0] = c_pre; cnt[1] = c_mask; cnt[2] = c_alpha; cnt[3] = c_shade;
+            k4c_shade<WIDTH>(G, N, p, R.vd, rgb);
+        },
+        [&](int k) { return (float)k; });
+    return k4w_walk<true, true>(M, lane, A.thres, A.counters != nullptr);
 }
 
 template <int WF, int WB>
 __global__ __launch_bounds__(64) void k_march_bivox(const K4BivoxArgs A) {
-    __shared__ int qk[128];
-    __shared__ float qw[128];
     const int64_t ray = blockIdx.x;
     if (ray >= A.n_rays) return;
     const int lane = k4_lane();
     K4BivoxRay R;
-    {
-        const float dx = A.rd[ray * 3 + 0], dy = A.rd[ray * 3 + 1], dz = A.rd[ray * 3 + 2];
-        const float dn = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        const float c[3] = {A.cx, A.cy, A.cz}, r[3] = {A.rx, A.ry, A.rz}, dv[3] = {dx, dy, dz};
+    k4w_unit_ray(A.ro, A.rd, ray, {A.cx, A.cy, A.cz}, {A.rx, A.ry, A.rz}, R.o, R.d);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            R.o[a] = __fdiv_rn(__fsub_rn(A.ro[ray * 3 + a], c[a]), r[a]);
-            R.d[a] = __fdiv_rn(dv[a], dn);
-            R.vd[a] = A.vd[ray * 3 + a];
-        }
-    }
+    for (int a = 0; a < 3; ++a) R.vd[a] = A.vd[ray * 3 + a];
     // sample_pts_on_rays of the unit cube, near 0 (k_pts_count / k_pts_fill)
     float t_min, t_max;
-    aabb_t(R.o, R.d, A.ph[0].mn, A.ph[0].mx, 0.f, A.far, 0, t_min, t_max);
+    aabb_t(R.o, R.d, A.G[0].mn, A.G[0].mx, 0.f, A.far, 0, t_min, t_max);
     const float rn = ray_norm(R.d, 0);
     int64_t n64 = n_steps_of(t_min, t_max, rn, A.stepdist);
     const int n_fg = (int)(n64 < 0 ? 0 : (n64 > (1 << 30) ? (1 << 30) : n64));
@@ -1749,28 +1530,28 @@ __global__ __launch_bounds__(64) void k_march_bivox(const K4BivoxArgs A) {
         R.dir[a] = R.d[a] / rn;
     }
     R.t_max = t_max;
-    float T_f, T_b = 1.f, sum_f[4], sum_b[4] = {0.f, 0.f, 0.f, 0.f};
-    int last_f, last_b = -1;
-    unsigned long long cnt_f[4], cnt_b[4] = {0, 0, 0, 0};
-    k4b_pass<WF, false>(A, A.ph[0], R, n_fg, lane, qk, qw, T_f, sum_f, last_f, cnt_f);
-    if (T_f > A.thres)                                     // lib/dbvgo.py:258-262 (applied whatever the threshold)
-        k4b_pass<WB, true>(A, A.ph[1], R, A.n_outer, lane, qk, qw, T_b, sum_b, last_b, cnt_b);
+    const K4WalkOut F = k4b_pass<WF, false>(A, A.G[0], A.N[0], R, n_fg, lane);
+    K4WalkOut B{1.f, {0.f, 0.f, 0.f, 0.f}, {0, 0, 0, 0}, -1};
+    if (F.T > A.thres) {                                     // lib/dbvgo.py:258-262 (applied whatever the threshold)
+        __syncthreads();                                     // the background pass refills the queue
+        B = k4b_pass<WB, true>(A, A.G[1], A.N[1], R, A.n_outer, lane);
+    }
     if (lane == 0) {
-        const float lf = fmaxf(0.f, (float)last_f);        // segment max seeded with 0, then with the foreground's (lib/dbvgo.py:382-391)
-        const float lb = fmaxf(lf, (float)last_b);
-        const float tt = __fmul_rn(T_f, T_b);
+        const float lf = fmaxf(0.f, (float)F.last);          // segment max seeded with 0, then with the foreground's (lib/dbvgo.py:382-391)
+        const float lb = fmaxf(lf, (float)B.last);
+        const float tt = __fmul_rn(F.T, B.T);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-            A.rgb[ray * 3 + c] = __fadd_rn(__fadd_rn(sum_f[c], __fmul_rn(T_f, sum_b[c])), __fmul_rn(tt, A.bg));
-        A.depth[ray] = __fadd_rn(__fadd_rn(sum_f[3], __fmul_rn(T_f, __fadd_rn(__fadd_rn(1.f, lf), sum_b[3]))),
+            A.rgb[ray * 3 + c] = __fadd_rn(__fadd_rn(F.sum[c], __fmul_rn(F.T, B.sum[c])), __fmul_rn(tt, A.bg));
+        A.depth[ray] = __fadd_rn(__fadd_rn(F.sum[3], __fmul_rn(F.T, __fadd_rn(__fadd_rn(1.f, lf), B.sum[3]))),
                                  __fmul_rn(tt, __fadd_rn(__fadd_rn(2.f, lf), lb)));
-        A.ainv_fg[ray] = T_f;
-        A.ainv_bg[ray] = T_b;
+        A.ainv_fg[ray] = F.T;
+        A.ainv_bg[ray] = B.T;
         if (A.counters != nullptr) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                atomicAdd(&A.counters[i], cnt_f[i]);
-                atomicAdd(&A.counters[4 + i], cnt_b[i]);
+                atomicAdd(&A.counters[i], F.cnt[i]);
+                atomicAdd(&A.counters[4 + i], B.cnt[i]);
             }
         }
     }
@@ -1786,23 +1567,15 @@ extern "C" int k4_march_bivox_fwd(const k4_bivox_desc* g, void* stream) {
     if (W1 != 0 && W1 != W0) return K4_ERR_UNSUPPORTED;
     K4BivoxArgs A;
     for (int i = 0; i < 2; ++i) {
-        REQ(g->density[i] && g->k0[i] && g->mask[i] && g->xyz2ijk_scale[i] && g->xyz2ijk_shift[i]);
-        REQ(g->dims[i][0] > 0 && g->dims[i][1] > 0 && g->dims[i][2] > 0 && g->mask_dims[i][0] > 0 && g->mask_dims[i][1] > 0 && g->mask_dims[i][2] > 0);
-        const int W = g->width[i];
-        if (W == 0) { REQ(g->k0_ch[i] == 3); }
+        REQ(k4_grid_fill(A.G[i], g->density[i], g->k0[i], true, g->k0_ch[i], g->dims[i], g->xyz_min, g->xyz_max, g->mask[i], g->mask_dims[i],
+                         g->xyz2ijk_scale[i], g->xyz2ijk_shift[i]));
+        A.N[i] = K4Net{};
+        if (g->width[i] == 0) { REQ(g->k0_ch[i] == 3); }
         else {
-            if (g->n_hidden[i] != 0 && g->n_hidden[i] != 1) return K4_ERR_UNSUPPORTED;
-            REQ(g->n_pe >= 0 && g->dim0[i] == g->k0_ch[i] + 3 + 6 * g->n_pe && (g->n_pe == 0 || g->viewfreq));
-            REQ(g->w1[i] && g->b1[i] && g->w3[i] && g->b3[i] && (g->n_hidden[i] == 0 || (g->w2[i] && g->b2[i])));
+            const int rc = k4_net_fill(A.N[i], g->width[i], false, g->n_hidden[i], K4_ERR_UNSUPPORTED, g->dim0[i], g->k0_ch[i] + 3 + 6 * g->n_pe, g->viewfreq,
+                                       g->n_pe, g->w1[i], g->b1[i], g->w2[i], g->b2[i], g->w3[i], g->b3[i]);
+            if (rc) return rc;
         }
-        K4ContractedArgs& P = A.ph[i];
-        P = K4ContractedArgs{};
-        P.density = g->density[i]; P.k0 = g->k0[i]; P.C = g->k0_ch[i]; P.X = g->dims[i][0]; P.Y = g->dims[i][1]; P.Z = g->dims[i][2];
-        P.mn = g->xyz_min; P.mx = g->xyz_max;
-        P.mask = g->mask[i]; P.MX = g->mask_dims[i][0]; P.MY = g->mask_dims[i][1]; P.MZ = g->mask_dims[i][2];
-        P.sc = g->xyz2ijk_scale[i]; P.sh = g->xyz2ijk_shift[i];
-        P.w1 = g->w1[i]; P.b1 = g->b1[i]; P.w2 = g->w2[i]; P.b2 = g->b2[i]; P.w3 = g->w3[i]; P.b3 = g->b3[i];
-        P.dim0 = g->dim0[i]; P.n_hidden = g->n_hidden[i]; P.viewfreq = g->viewfreq; P.n_pe = g->n_pe;
     }
     A.ro = g->rays_o; A.rd = g->rays_d; A.vd = g->viewdirs; A.n_rays = g->n_rays;
     A.cx = g->scene_center[0]; A.cy = g->scene_center[1]; A.cz = g->scene_center[2];

@@ -341,12 +341,7 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
         memory.  Returns alphainv_last (cat([fg, bg]), 2N), rgb_marched (= rgb_feature) and, with render_depth, depth."""
         Nr = rays_o.shape[0]
         dev = rays_o.device
-        rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
-        depth = torch.empty([Nr], dtype=torch.float32, device=dev)
-        ainv = torch.empty([2 * Nr], dtype=torch.float32, device=dev)
-        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
-        if render_depth:
-            ret['depth'] = depth
+        rgb, depth, ainv, ret = self._k4_ray_outputs(Nr, dev, render_depth, n_ainv=2)
         if Nr == 0:
             return ret
 
@@ -378,13 +373,8 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
                 if net is None:
                     d.width[i] = 0
                     continue
-                lins = [m for m in net.modules() if isinstance(m, nn.Linear)]
-                ws = [t.detach().float().contiguous() for l in lins for t in (l.weight, l.bias)]
+                ws, (d.dim0[i], d.width[i], d.n_hidden[i]) = self._k4_rgbnet_into(net, d, i)
                 keep += ws
-                d.w1[i], d.b1[i], d.w3[i], d.b3[i] = ws[0].data_ptr(), ws[1].data_ptr(), ws[-2].data_ptr(), ws[-1].data_ptr()
-                if len(lins) == 3:
-                    d.w2[i], d.b2[i] = ws[2].data_ptr(), ws[3].data_ptr()
-                d.dim0[i], d.width[i], d.n_hidden[i] = lins[0].in_features, lins[0].out_features, len(lins) - 2
             return d, keep
         d = self._k4_plan('dbvgo', (float(stepsize), float(self.fast_color_thres), float(self.bg_preserve), float(self.voxel_size),
                                     float(self.voxel_size_ratio)) + tuple(
@@ -393,12 +383,7 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
         d.bg = float(bg)
         d.rgb, d.depth = rgb.data_ptr(), depth.data_ptr()
         d.alphainv_fg, d.alphainv_bg = ainv.data_ptr(), ainv.data_ptr() + 4 * Nr
-        if k4_counters is not None:
-            if k4_counters.dtype != torch.int64 or k4_counters.numel() < 8 or not k4_counters.is_cuda:
-                raise N.K4Error('k4_counters: int64 device tensor of >= 8 words')
-            d.counters = k4_counters.data_ptr()
-        else:
-            d.counters = None
+        d.counters = self._k4_counters_ptr(k4_counters, 8)
         rc = N.lib().k4_march_bivox_fwd(N.C.byref(d), N.stream())
         if rc == N.K4_ERR_UNSUPPORTED:              # a shape outside the fused kernel: the staged ops
             return self._forward_staged(rays_o, rays_d, viewdirs, stepsize=stepsize, bg=bg, render_depth=render_depth)

@@ -281,12 +281,7 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
         Returns alphainv_last, rgb_marched (= rgb_feature) and, with render_depth, depth."""
         Nr = rays_o.shape[0]
         dev = rays_o.device
-        rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
-        depth = torch.empty([Nr], dtype=torch.float32, device=dev)
-        ainv = torch.empty([Nr], dtype=torch.float32, device=dev)
-        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
-        if render_depth:
-            ret['depth'] = depth
+        rgb, depth, ainv, ret = self._k4_ray_outputs(Nr, dev, render_depth)
         if Nr == 0:
             return ret
 
@@ -314,13 +309,8 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
             if self.rgbnet is None:
                 d.width = 0
             else:
-                lins = [m for m in self.rgbnet.modules() if isinstance(m, nn.Linear)]
-                ws = [t.detach().float().contiguous() for l in lins for t in (l.weight, l.bias)]
+                ws, (d.dim0, d.width, d.n_hidden) = self._k4_rgbnet_into(self.rgbnet, d)
                 keep += ws
-                d.w1, d.b1, d.w3, d.b3 = ws[0].data_ptr(), ws[1].data_ptr(), ws[-2].data_ptr(), ws[-1].data_ptr()
-                if len(lins) == 3:
-                    d.w2, d.b2 = ws[2].data_ptr(), ws[3].data_ptr()
-                d.dim0, d.width, d.n_hidden = lins[0].in_features, lins[0].out_features, len(lins) - 2
                 d.viewfreq, d.n_pe = self.viewfreq.data_ptr(), int(self.viewfreq.numel())
             return d, keep
         d = self._k4_plan('dcvgo', (float(stepsize), float(self.fast_color_thres), float(self.bg_len), int(self.world_len),
@@ -329,12 +319,7 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
         d.rays_o, d.rays_d, d.viewdirs, d.n_rays = rays_o.data_ptr(), rays_d.data_ptr(), viewdirs.data_ptr(), Nr
         d.bg = float(bg)
         d.rgb, d.depth, d.alphainv_last = rgb.data_ptr(), depth.data_ptr(), ainv.data_ptr()
-        if k4_counters is not None:
-            if k4_counters.dtype != torch.int64 or k4_counters.numel() < 4 or not k4_counters.is_cuda:
-                raise N.K4Error('k4_counters: int64 device tensor of >= 4 words')
-            d.counters = k4_counters.data_ptr()
-        else:
-            d.counters = None
+        d.counters = self._k4_counters_ptr(k4_counters, 4)
         N.check(N.lib().k4_march_contracted_fwd(N.C.byref(d), N.stream()), 'k4_march_contracted_fwd')
         return ret
 

@@ -323,6 +323,41 @@ class _FusedMarcher:
             c[name + '_key'], c[name] = key, float(t)
         return c[name]
 
+    # ---- shared by the one-launch marchers (k4_march_contracted_fwd, k4_march_bivox_fwd, k4_march_vq_fwd)
+    @staticmethod
+    def _k4_ray_outputs(n_rays, device, render_depth, n_ainv=1):
+        """-> rgb [N,3], depth [N], alphainv_last [n_ainv N] for the kernel to fill, and the dict a forward returns (depth only on request)."""
+        rgb = torch.empty([n_rays, 3], dtype=torch.float32, device=device)
+        depth = torch.empty([n_rays], dtype=torch.float32, device=device)
+        ainv = torch.empty([n_ainv * n_rays], dtype=torch.float32, device=device)
+        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
+        if render_depth:
+            ret['depth'] = depth
+        return rgb, depth, ainv, ret
+
+    @staticmethod
+    def _k4_rgbnet_into(net, d, i=None):
+        """Point descriptor ``d`` (its slot ``i`` where the fields are arrays) at the nn.Linear tensors of ``net`` as w1, b1, [w2, b2,] w3, b3.
+        -> (the contiguous fp32 tensors to keep alive, (dim0, width, n_hidden))."""
+        lins = [m for m in net.modules() if isinstance(m, nn.Linear)]
+        ws = [t.detach().float().contiguous() for l in lins for t in (l.weight, l.bias)]
+        names = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3') if len(lins) == 3 else ('w1', 'b1', 'w3', 'b3')
+        for name, w in zip(names, ws):
+            if i is None:
+                setattr(d, name, w.data_ptr())
+            else:
+                getattr(d, name)[i] = w.data_ptr()
+        return ws, (lins[0].in_features, lins[0].out_features, len(lins) - 2)
+
+    @staticmethod
+    def _k4_counters_ptr(k4_counters, words):
+        """The ``counters`` field of a descriptor: None, or the pointer of an int64 device tensor of at least ``words`` words."""
+        if k4_counters is None:
+            return None
+        if k4_counters.dtype != torch.int64 or k4_counters.numel() < words or not k4_counters.is_cuda:
+            raise N.K4Error(f'k4_counters: int64 device tensor of >= {words} words')
+        return k4_counters.data_ptr()
+
     @staticmethod
     def _k4_check_rays(rays_o, rays_d, viewdirs):
         assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'

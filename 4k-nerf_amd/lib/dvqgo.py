@@ -119,37 +119,28 @@ class DirectQVGO(DirectMPIGO):
         """Inference in ONE launch (k4_march_vq_fwd): rgb_marched (= rgb_feature), alphainv_last and, on request, depth."""
         assert near == 0 and far == 1                                     # lib/dvqgo.py:262
         Nr, dev = rays_o.shape[0], rays_o.device
-        rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
-        depth = torch.empty([Nr], dtype=torch.float32, device=dev)
-        ainv = torch.empty([Nr], dtype=torch.float32, device=dev)
+        rgb, depth, ainv, ret = self._k4_ray_outputs(Nr, dev, render_depth)
         N_samples = int((self.mpi_depth - 1) / stepsize) + 1              # lib/dvqgo.py:265
-        lins = [m for m in self.rgbnet.modules() if isinstance(m, torch.nn.Linear)]
         mc, k0, dens, act = self.mask_cache, self.k0, self.density.grid, self.act_shift.grid
         keep = [rays_o, rays_d, viewdirs, dens.detach().contiguous(), act.detach().contiguous(), mc.mask.contiguous(), k0.prepared_codebook()]
         keep += [t.detach().float().contiguous() for t in (self.xyz_min, self.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift, self.posfreq,
                                                            k0.project_layer[0].weight, k0.project_layer[0].bias, k0.project_layer[2].weight,
                                                            k0.project_layer[2].bias)]
-        keep += [t.detach().float().contiguous() for l in lins for t in (l.weight, l.bias)]
         p = [t.data_ptr() or None for t in keep]
         d = N.VqDesc()
+        ws, (d.dim0, d.width, d.n_hidden) = self._k4_rgbnet_into(self.rgbnet, d)
+        keep += ws
         d.rays_o, d.rays_d, d.viewdirs, d.density, d.act_shift, d.mask, d.codebook = p[:7]
         d.xyz_min, d.xyz_max, d.xyz2ijk_scale, d.xyz2ijk_shift, d.posfreq, d.pw1, d.pb1, d.pw2, d.pb2 = p[7:16]
-        d.w1, d.b1 = p[16:18]
-        d.w3, d.b3 = p[-2:]
-        if len(lins) == 3:
-            d.w2, d.b2 = p[18:20]
         d.n_rays, d.n_samples = Nr, N_samples
         d.dims = (N.C.c_int32 * 3)(*[int(v) for v in dens.shape[2:]])
         d.act_depth = int(act.numel())
         d.mask_dims = (N.C.c_int32 * 3)(*[int(v) for v in mc.mask.shape])
         d.interval, d.fast_color_thres, d.bg = float(stepsize * self.voxel_size_ratio), float(self.fast_color_thres), float(bg)
         d.n_pe, d.dim, d.n_embed = int(self.posfreq.numel()), k0.dim, k0.n_embed
-        d.dim0, d.width, d.n_hidden = lins[0].in_features, lins[0].out_features, len(lins) - 2
         d.rgb, d.depth, d.alphainv_last = rgb.data_ptr() or None, depth.data_ptr() or None, ainv.data_ptr() or None
         if any(not t.is_cuda for t in keep):
             raise N.K4Error('DirectQVGO.forward: every tensor of the model must be on the GPU (no CPU path)')
         N.check(N.lib().k4_march_vq_fwd(N.C.byref(d), N.stream()), 'k4_march_vq_fwd')
-        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb, 'n_max': N_samples}
-        if render_depth:
-            ret['depth'] = depth
+        ret['n_max'] = N_samples
         return ret

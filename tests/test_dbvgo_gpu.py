@@ -334,3 +334,59 @@ def test_render_viewpoints_and_parameter_changes():
         staged3 = model(ro, rd, vd, k4_staged=True, **rk)
     assert not torch.equal(third['rgb_marched'], again['rgb_marched'])
     assert float((third['rgb_marched'] - staged3['rgb_marched']).abs().max()) <= 1e-5
+
+
+def test_one_launch_with_more_than_64_survivors_on_a_ray_and_without_thresholds():
+    """The twin of test_vq_gpu.py's test of this name on k_march_bivox.  fast_color_thres = 0 on two all-occupied masks: every in-box sample in
+    front of the T < 1e-3 stop is shaded, so a ray queues more than 64 survivors -- the queue is flushed mid-ray and its rest moved -- and shades
+    in its third 64-lane chunk (36^3 voxels, stepsize 0.25; 24x32 frame, width 32 in both passes).  Without a threshold every in-mask sample is
+    kept, also behind the stop, and the background is walked whatever T_fg is: the last kept step of both passes enters depth.  The frame contract
+    of tests/test_march_gpu.py between the one launch and the staged path (>= 99.9 % of the rays within 2e-5, every ray within 2e-3) on rgb,
+    alphainv_last and depth -- depth, a weighted sum of step indices, on the scale of its formula (bivox_oracle.depth_scale) as everywhere in this
+    file: fp32 does not resolve 2e-5 on values of several hundred; the same bits with and without counters; no weight filter: n_shade == n_alpha
+    in both passes.
+    Measured on an MI355X with the library of the commit before the shared walk: 175 weighted foreground samples on the fullest ray (last weighted
+    step 174) and 63 background ones, 39 of 768 rays stop in the foreground, every ray has background survivors; 100 % of the rays within 2e-5
+    for all three outputs, largest 1.5e-6 (rgb), 1.2e-6 of its scale 238 (depth), 8.3e-7 (alphainv_last); counters 103924 four times for the
+    foreground, 48384 for the background."""
+    ck = scene.make_bivox_checkpoint(seed=58, num_voxels=36 ** 3, rgbnet_dim=6, rgbnet_width=32, fast_color_thres=0, stepsize=0.25, n_blobs=5)
+    for i in range(2):
+        ck['model_state_dict'][f'mask_cache.{i}.mask'] = torch.ones_like(ck['model_state_dict'][f'mask_cache.{i}.mask'])
+    model = _model(ck).eval()
+    assert model._k4_fusable() and float(model.fast_color_thres) == 0
+    ro, rd, vd = _frame_rays(24, 32, 1)
+    n, rk = ro.shape[0], ck['render_kwargs']
+    cnt = torch.zeros(8, dtype=torch.int64, device='cuda')
+    with torch.no_grad():
+        staged = model(ro, rd, vd, k4_staged=True, **rk)
+        fused = model(ro, rd, vd, **rk)
+        counted = model(ro, rd, vd, k4_counters=cnt, **rk)
+        # the staged path's two passes one by one (_forward_staged's calls): steps and weights per pass
+        pts, ray_id, step_id, outer = model.sample_ray(ori_rays_o=ro, ori_rays_d=rd, stepsize=rk['stepsize'])
+        both = dict(viewdirs=vd, interval=rk['stepsize'] * model.voxel_size_ratio, N_=n)
+        fg = model._forward(ray_pts=pts, mask_grid=model.mask_cache[0], density_grid=model.density[0], k0_grid=model.k0[0], rgbnet=model._rgbnet_of(0),
+                            ray_id=ray_id, step_id=step_id, **both)
+        bgp = model._forward(ray_pts=outer, mask_grid=model.mask_cache[1], density_grid=model.density[1], k0_grid=model.k0[1], rgbnet=model._rgbnet_of(1),
+                             prev_alphainv_last=fg['alphainv_last'], **both)
+    assert torch.equal(torch.cat([fg['weights'], bgp['weights']]), staged['weights'])
+    T_fg = fg['alphainv_last']
+    per_ray = [torch.bincount(p['ray_id'][p['weights'] > 0], minlength=n) for p in (fg, bgp)]
+    last = [int(p['step_id'][p['weights'] > 0].max()) for p in (fg, bgp)]
+    walked_bg = torch.bincount(bgp['ray_id'], minlength=n) > 0
+    stops_fg = T_fg < 1e-3
+    print(f'most weighted samples on a ray fg {int(per_ray[0].max())} bg {int(per_ray[1].max())}, last weighted step fg {last[0]} bg {last[1]}, '
+          f'rays stopping in the foreground {int(stops_fg.sum())}, rays with background survivors {int((per_ray[1] > 0).sum())} of {n}')
+    assert 'weights' not in fused and int(per_ray[0].max()) > 64 and max(last) >= 128
+    assert int(stops_fg.sum()) > 0 and bool(walked_bg[stops_fg].all())          # T_fg <= 0 never holds: the background is walked behind a stop too
+    assert int(((per_ray[1] > 0) & ~stops_fg).sum()) > 0
+    ds = bo.depth_scale(ck['model_kwargs'], int(fg['step_id'].max()), rk['stepsize'])
+    for k in ('rgb_marched', 'depth', 'alphainv_last'):
+        s = ds if k == 'depth' else 1.0
+        d = (fused[k] - staged[k]).abs() / s
+        d = d.amax(-1) if d.dim() > 1 else d
+        print(f'{k}: max|err| {float(d.max()):.3e} (scale {s}), within 2e-5: {float((d <= 2e-5).float().mean()):.5f}')
+        assert float((d <= 2e-5).float().mean()) >= 0.999 and float(d.max()) <= 2e-3, (k, float(d.max()))
+        assert torch.equal(fused[k], counted[k]), k
+    c = cnt.cpu().tolist()
+    print('counters', c)
+    assert c[3] == c[2] > 0 and c[7] == c[6] > 0

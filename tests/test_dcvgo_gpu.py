@@ -289,3 +289,38 @@ def test_joint_step_with_nearclip_and_distortion():
         a = dcvgo.distortion_loss(rr['weights'], rr['s'], rr['n_max'], rr['ray_id'])
         a.backward()
     assert torch.isfinite(a) and model.density.grid.grad is not None
+
+
+def test_one_launch_with_more_than_64_survivors_on_a_ray_and_without_thresholds():
+    """The twin of test_vq_gpu.py's test of this name on k_march_contracted.  fast_color_thres = 0 on an all-occupied mask: every sample that passes
+    inner | cumdist in front of the T < 1e-3 stop is shaded, so a ray queues more than 64 survivors -- the queue is flushed mid-ray and its rest
+    moved -- and shades in its third 64-lane chunk (36^3 voxels, stepsize 0.25: 242 steps per ray; 24x32 frame, width 32).  The frame contract of
+    tests/test_march_gpu.py between the one launch and the staged path (>= 99.9 % of the rays within 2e-5, every ray within 2e-3), depth included;
+    the same bits with and without counters; no weight filter: n_shade == n_alpha.
+    Measured on an MI355X with the library of the commit before the shared walk: 167 weighted samples on the fullest ray, last weighted step 241 of
+    242; 100 % of the 768 rays within 2e-5 for all three outputs, largest 9.5e-7 (rgb), 1.1e-6 (depth), 1.6e-6 (alphainv_last); counters
+    106968 four times."""
+    ck = scene.make_unbounded_checkpoint(seed=57, num_voxels=36 ** 3, rgbnet_dim=6, rgbnet_width=32, fast_color_thres=0, stepsize=0.25, n_blobs=4)
+    ck['model_state_dict']['mask_cache.mask'] = torch.ones_like(ck['model_state_dict']['mask_cache.mask'])
+    model = _model(ck).eval()
+    assert model._k4_fusable() and float(model.fast_color_thres) == 0
+    ro, rd, vd = _frame_rays(24, 32, 1)
+    cnt = torch.zeros(4, dtype=torch.int64, device='cuda')
+    with torch.no_grad():
+        staged = model(ro, rd, vd, k4_staged=True, **ck['render_kwargs'])
+        fused = model(ro, rd, vd, **ck['render_kwargs'])
+        counted = model(ro, rd, vd, k4_counters=cnt, **ck['render_kwargs'])
+    live = staged['weights'] > 0                                  # (the staged path keeps the zero-weight samples behind the stop)
+    per_ray = torch.bincount(staged['ray_id'][live], minlength=ro.shape[0])
+    last = int(staged['step_id'][live].max())
+    print(f'most weighted samples on a ray {int(per_ray.max())}, last weighted step {last} of {staged["n_max"]}')
+    assert 'weights' not in fused and int(per_ray.max()) > 64 and last >= 128
+    for k in ('rgb_marched', 'depth', 'alphainv_last'):
+        d = (fused[k] - staged[k]).abs()
+        d = d.amax(-1) if d.dim() > 1 else d
+        print(f'{k}: max|err| {float(d.max()):.3e}, within 2e-5: {float((d <= 2e-5).float().mean()):.5f}')
+        assert float((d <= 2e-5).float().mean()) >= 0.999 and float(d.max()) <= 2e-3, (k, float(d.max()))
+        assert torch.equal(fused[k], counted[k]), k
+    c = cnt.cpu().tolist()
+    print('counters', c)
+    assert c[3] == c[2] > 0 and c[0] >= c[1] >= c[2]

@@ -41,10 +41,10 @@ with torch.no_grad():
             torch.cuda.synchronize()
             if i >= 1:
                 ms.append(a.elapsed_time(b))
-        return float(np.median(ms)), r
+        return float(np.median(ms)), r, f'{min(ms):.2f} .. {max(ms):.2f}, {len(ms)} runs'
 
     # fused: ONE call for the whole frame (k4_march_contracted_fwd, no workspace)
-    fused_ms, out_f = timed(lambda: model(ro, rd, vd, **rk))
+    fused_ms, out_f, fused_span = timed(lambda: model(ro, rd, vd, **rk))
     cnt = torch.zeros(8, dtype=torch.int64, device=dev)
     model(ro, rd, vd, k4_counters=cnt, **rk)
     c = cnt.cpu().tolist()
@@ -55,13 +55,13 @@ with torch.no_grad():
         for s in range(0, n_rays, args.chunk):
             n += model(ro[s:s + args.chunk], rd[s:s + args.chunk], vd[s:s + args.chunk], k4_staged=True, **rk)['ray_id'].shape[0]
         return n
-    staged_ms, n_staged = timed(staged)
+    staged_ms, n_staged, _ = timed(staged)
     n_max = len(model._step_table(rk['stepsize'], dev))
     agree = float((out_f['rgb_marched'] - torch.cat([model(ro[s:s + args.chunk], rd[s:s + args.chunk], vd[s:s + args.chunk], k4_staged=True, **rk)['rgb_marched']
                                                      for s in range(0, n_rays, args.chunk)])).abs().max())
 table_est = args.chunk * n_max * (3 * 4 * 3 + 4 + 1 + 1)     # ESTIMATE (not measured): the staged chunk's [chunk][n_max] point / difference / dist / mask tables
 print(f'DirectContractedVoxGO {args.voxels}^3, {W}x{H}, {n_max} steps per ray ({n_rays * n_max} per frame)')
-print(f'  fused (1 launch, workspace 0 bytes): median {fused_ms:.2f} ms per frame = {n_rays / fused_ms / 1e3:.1f} Mrays/s')
+print(f'  fused (1 launch, workspace 0 bytes): median {fused_ms:.2f} ms per frame ({fused_span}) = {n_rays / fused_ms / 1e3:.1f} Mrays/s')
 print(f'  staged ({args.chunk}-ray chunks): median {staged_ms:.1f} ms per frame = {n_rays / staged_ms / 1e3:.2f} Mrays/s; '
       f'its per-chunk step tables ~{table_est / 1e9:.2f} GB (estimate)')
 print(f'  sample counters (fused): inner|cumdist {c[0]}, mask-pass {c[1]}, alpha-pass {c[2]}, shaded {c[3]} (staged shaded {n_staged}); '

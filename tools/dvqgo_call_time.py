@@ -50,7 +50,7 @@ def once(fn):
 
 
 def stats(v):
-    return f'{np.median(v):.3f} (p10 {np.percentile(v, 10):.3f}, p90 {np.percentile(v, 90):.3f})'
+    return f'{np.median(v):.3f} (p10 {np.percentile(v, 10):.3f}, p90 {np.percentile(v, 90):.3f}, {np.min(v):.3f} .. {np.max(v):.3f})'
 
 
 X, Y, Z = args.voxels
