@@ -2,6 +2,10 @@
 
 hipcc cross-compiles without a GPU.  Objects are cached by source mtime; the .so sits next to this
 file so it travels to the GPU box with the repo snapshot (git-ignored, not gpurun-ignored).
+
+A variant library for A/B runs (loaded through K4_LIB): python build.py --tag TAG [-DNAME[=VALUE] ...] [--force] compiles EVERY source
+with the extra -D flags into build_TAG/ and links lib4k_hip_TAG.so; the default build is untouched.  The object cache does not know
+the flags: pass --force when a tag's flags change.  The ablation build (csrc/k4_env.h): --tag ablate -DK4_ABLATE.
 """
 import os
 import subprocess
@@ -26,9 +30,10 @@ def _newer(a, b):
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-def build(verbose=False, force=False):
+def build(verbose=False, force=False, tag=None, defines=()):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objdir = os.path.join(PKG, 'build')
+    objdir = os.path.join(PKG, 'build_' + tag if tag else 'build')
+    out = os.path.join(PKG, 'lib4k_hip_%s.so' % tag) if tag else OUT
     os.makedirs(objdir, exist_ok=True)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + \
            [os.path.join(ROOT, 'include', 'k4nerf.h')]
@@ -39,19 +44,25 @@ def build(verbose=False, force=False):
             continue
         o = os.path.join(objdir, src + '.o')
         if force or _newer(s, o) or any(_newer(d, o) for d in deps):
-            cmd = [hipcc] + FLAGS + ['-c', s, '-o', o]
+            cmd = [hipcc] + FLAGS + list(defines) + ['-c', s, '-o', o]
             if verbose:
                 print(' '.join(cmd), flush=True)
             subprocess.check_call(cmd)
             relink = True
         objs.append(o)
-    if relink or not os.path.exists(OUT) or any(_newer(o, OUT) for o in objs):
-        cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', OUT] + objs
+    if relink or not os.path.exists(out) or any(_newer(o, out) for o in objs):
+        cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', out] + objs
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.check_call(cmd)
-    return OUT
+    return out
 
 
 if __name__ == '__main__':
-    print(build(verbose=True, force='--force' in sys.argv))
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--force', action='store_true', help='recompile every source')
+    ap.add_argument('--tag', help='variant build: objects in build_TAG/, library lib4k_hip_TAG.so')
+    ap.add_argument('-D', dest='defines', action='append', default=[], metavar='NAME[=VALUE]', help='extra macro for every source')
+    a = ap.parse_args()
+    print(build(verbose=True, force=a.force, tag=a.tag, defines=['-D' + d for d in a.defines]))

@@ -5,6 +5,7 @@
 #include <functional>
 #include <vector>
 #include "k4nerf.h"
+#include "k4_env.h"
 
 #define K4_WAVE 64
 
@@ -143,21 +144,13 @@ static inline int k4_check_launch() {
 }
 
 // ---- host-side process state: none that can change after load --------------------------------------------------------
-// Experiment / profiling knobs are environment variables read ONCE while the library is being loaded (a namespace-scope
-// constant in k4_march.hip); launches never call getenv.  Per-device facts (CU count, "dynamic LDS attribute already raised
+// Experiment / profiling knobs are environment variables read ONCE while the library is being loaded (K4Env, the namespace-scope
+// constant of k4_env.h); launches never call getenv.  Per-device facts (CU count, "dynamic LDS attribute already raised
 // for kernel F") are cached in fixed arrays indexed by the HIP device ordinal; concurrent first calls write the same values.
-struct K4Env {
-    int geom_skip;       // K4_GEOM_SKIP    (1) 0: do not use the coarse occupancy summary (A/B of the empty-space skipping)
-    int debug;           // K4_DEBUG        (0) ablation bits of the marcher kernels, profiling only
-    int sr_debug;        // K4_SR_DEBUG     (0) profiling bits of the decoder kernels (1: input channel stride 0 = no memory traffic, WRONG results; 2..16: phases of the 3x3 kernel off; 32: SFT layers on the unpipelined kernel; exact ones: 2048: row kernel instead of the K-split 3x3 kernel on small images, 4096: per-tap weight-gradient kernel instead of the nine-tap one)
-    bool no_fast_shade;  // K4_DEBUG & 1024: the shading kernel's general path on shapes the FAST path covers (A/B, tests: identical outputs)
-    bool no_fast_geom;   // K4_DEBUG & 16384: the geometry kernel's general path on shapes its FAST path covers (A/B, tests: identical outputs)
-};
 // Settled by measurement and no longer switchable (the evidence is in profiles/ and DESIGN.md): geometry kernel bounded for 5 waves per
 // SIMD (6 spilled), serpentine ray order inside an 8x8 tile, one row of workgroup tiles per XCD band, persistent shading grid of 2 workgroups
 // per CU (K4_SHADE_WG_PER_CU, a compile-time constant), small-launch tile rule of the 3x3 convolution on, 16-row tiles for the 3-term kernel and 8-row tiles for the
 // 2-term (f16x3) kernel beyond it (8-row 37.1 ms per 4K frame, 12-row 39.3, 16-row 38.5-38.8).
-const K4Env& k4_env();
 #define K4_MAX_DEVICES 64
 static inline int k4_device_ordinal() {
     int dev = 0;

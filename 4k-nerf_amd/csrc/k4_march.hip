@@ -72,7 +72,9 @@ struct MarchParams {
     int split_k;            // MPI: > 0 = depth-ordered geometry stage -- samples [0, split_k) in a first launch, [split_k, n_samples) in a second one that
                             // drops every ray the first launch's transmittance scan stopped (k4_grid_desc.depth_split; a multiple of 64)
     int slab;               // 0: the whole depth range in one launch; 1 / 2: first / second launch of the split form
-    int debug;              // K4_DEBUG ablation bits (profiling only; 0 in production)
+    int ablate;             // K4Env.ablate: K4_DEBUG ablation bits (profiling only, WRONG results).  Only a -DK4_ABLATE build can set one: the product
+                            // library keeps this 0 whatever the environment says (k4_env.h).  The two kernels test the field itself, not K4_ABL: with the
+                            // branches compiled out the register allocation of both got worse (profiles/ablate_build.md)
     int serp;               // 1: serpentine ray order inside a tile (default)
     int band_blocks;        // geometry kernel: blocks per XCD band (0: one contiguous band per XCD)
     float* out_rgb; float* out_depth; float* out_ainv; unsigned long long* counters;
@@ -187,7 +189,6 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 #define K4_TKTAB 256              // MPI: k/(Ns-1) for k < K4_TKTAB is tabulated once per workgroup (an IEEE division costs ~10 VALU per sample)
 #define K4_ELIST 512              // kept (ray, group) entries enumerated at a time (ray sub-batches when 64 rays x groups exceed it)
 #define K4_GRP 16                 // samples per skip group
-#define K4_GEOM_DEBUG_BITS (16 | 32 | 128 | 4096 | 8192)      // the K4_DEBUG ablation bits the geometry kernel reads (general instantiation only)
 struct Geom2Lds {
     float raytab[64][8];     // [0..2] start xyz, [3] bits(kq0) | [4..6] dir xyz, [7] bits(kq1): the bundle's rays and THIS wave's depth range [kq0,kq1) of each
                              // (FAST: [3] = the wave's group offset (w - (r >> 4)) & 3 inside every depth quarter of the ray, [7] = nsteps)
@@ -226,7 +227,8 @@ __device__ __forceinline__ float tk_of(const MarchParams& P, const float* tktab,
 // division fallback and its branch), Z >= 2, no ablation bit.  It drops code these conditions make dead and deals the groups to other waves (above):
 // every expression tree of a sample is the general path's and a ray's records reach the scan in the same depth order -> the same bits
 // (tests/test_geom_fast_gpu.py, test_geom_tail_gpu.py, test_geom_deal_gpu.py).  Bounded for 7 waves per SIMD (71 VGPRs, no spill): its residency
-// is the 7 workgroups per CU that 22.5 KB of LDS admit.  The host predicate is in launch_march; K4_DEBUG & 16384 forces the general path.
+// is the 7 workgroups per CU that 22.5 KB of LDS admit.  The host predicate is in launch_march; K4_DEBUG & 16384 (K4Env.no_fast_geom,
+// an exact selector every build honours) forces the general path, and so does a geometry ablation bit (K4_GEOM_ABLATE_BITS, -DK4_ABLATE builds only).
 template <int MODE, bool COUNT, int MINW, bool FAST = false>
 __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const MarchParams P) {
     static_assert(!FAST || (MODE == MODE_MPI && !COUNT), "FAST is the MPI render instantiation");
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
     __syncthreads();
     const bool unit_interval = FAST || P.interval == 1.f;
     const bool use_thres = FAST || P.thres > 0.f;
-    const int dbg = FAST ? 0 : P.debug;                                // ablation bits (general path only)
+    const int abl = FAST ? 0 : P.ablate;                               // ablation bits (general path only; 0 unless a -DK4_ABLATE build set one)
     auto tk_at = [&](int k) -> float { if constexpr (FAST) return tktab[k]; else return tk_of<MODE>(P, tktab, k); };
     unsigned long long n_inb = 0, n_mask = 0, n_alpha = 0, n_shade = 0, n_behind = 0;
 
@@ -312,8 +314,8 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
         L.acnt[lane] = 0;
     }
     K4_GSTAMP(0);                                                                // workgroup prologue + ray setup
-    if (dbg & 4096) ngrp = 0;                                                // ablation (WRONG results): prologue, arrival and the empty scan only -- the kernel's fixed cost
-    if (dbg & 8192) { if (lane == 0 && wv == 0) P.counts[B.id] = 0; break; } // ablation: not even the arrival / scan
+    if (abl & 4096) ngrp = 0;                                           // ablation (WRONG results): prologue, arrival and the empty scan only -- the kernel's fixed cost
+    if (abl & 8192) { if (lane == 0 && wv == 0) P.counts[B.id] = 0; break; } // ablation: not even the arrival / scan
     int gq = ngrp;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) gq = max(gq, __shfl_xor(gq, off));
@@ -399,7 +401,7 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
             const unsigned r00 = (unsigned)(x0 * P.Y + y0) * (unsigned)P.Z, r01 = (unsigned)(x0 * P.Y + y1) * (unsigned)P.Z;
             const unsigned r10 = (unsigned)(x1 * P.Y + y0) * (unsigned)P.Z, r11 = (unsigned)(x1 * P.Y + y1) * (unsigned)P.Z;
             pkey[s2] = key; pfx[s2] = ux; pfy[s2] = uy; pfz[s2] = uz;
-            if (dbg & 16) {                                           // ablation: no density fetch
+            if (abl & 16) {                                          // ablation: no density fetch
                 const float c = __uint_as_float(0x3f000000u + (r00 & 0xffffu));
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) pdl[s2][c4] = pdh[s2][c4] = c;
@@ -698,7 +700,7 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) maxc = max(maxc, __shfl_xor(maxc, off));
             maxc = __builtin_amdgcn_readfirstlane(maxc);
-            if (dbg & 32) maxc = 0;                                    // ablation: no transmittance scan
+            if (abl & 32) maxc = 0;                                   // ablation: no transmittance scan
             // (the NEXT four alphas are requested before the current four are folded into T: the loop is a load -> dependent chain -> store
             //  sequence per iteration, 25 % of the kernel's wave time in round 5's form)
             float an[4];
@@ -737,7 +739,7 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
             const uint2* const run = ent_base + run0 + (size_t)w * quarter;
             int naw = na_sh[w];
             na_all += naw;
-            if (dbg & 128) naw = 0;                                    // ablation: no survivor compaction (nothing shaded)
+            if (abl & 128) naw = 0;                                   // ablation: no survivor compaction (nothing shaded)
             for (int base = 0; base < naw; base += 64) {
                 const int i = base + lane;
                 const bool v = i < naw;
@@ -1021,8 +1023,8 @@ __global__ __launch_bounds__(256, WG) void k4_shade_kernel(const MarchParams P) 
             constexpr int NT2 = ARITH == 3 ? 3 : 2, NT1 = ARITH == 3 ? 3 : K4_B2_L1_TERMS;
             if constexpr (K4_MLP_PAIR && W == 64 && NHID == 1) {
                 if (nproc > 32) mlp_pair64<NT1, NT2>(wl, fs, lane, half, o0, o1, o2 K4_TPASS);
-                else mlp_mfma_bx<W, NHID, NT1, NT2, RegFeat, true>(wl, fs, 16, lane, half, P.debug, nproc, o0, o1, o2 K4_TPASS);
-            } else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, 16, lane, half, P.debug, nproc, o0, o1, o2 K4_TPASS);
+                else mlp_mfma_bx<W, NHID, NT1, NT2, RegFeat, true>(wl, fs, 16, lane, half, P.ablate, nproc, o0, o1, o2 K4_TPASS);
+            } else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, 16, lane, half, P.ablate, nproc, o0, o1, o2 K4_TPASS);
         } else if (WIDTH == 0) {
             // rgbnet is None: rgb = sigmoid(k0)   (lib/dvgo.py:377-379)
             float v[3] = {0.f, 0.f, 0.f};
@@ -1039,7 +1041,7 @@ __global__ __launch_bounds__(256, WG) void k4_shade_kernel(const MarchParams P) 
         } else {
             // ---------------- features -> LDS feat[k][sample] ----------------
             float dif0 = 0.f, dif1 = 0.f, dif2 = 0.f;                // k0[:, :3] when rgbnet_direct=False
-            if (P.k0_layout != K4_K0_CHANNEL_MAJOR && P.CP == 12 && !(P.debug & 1)) {
+            if (P.k0_layout != K4_K0_CHANNEL_MAJOR && P.CP == 12 && !(P.ablate & 1)) {
                 // (NOT k4_gather12 + a copy loop: that form -- all 12 channels blended first, then written to LDS -- compiled to a stream
                 // whose results differed from run to run in ~80 of the LLFF frame's 762,048 rays on the MI355X, by up to 5e-3; this
                 // form, stores interleaved with the channel groups, is bit-reproducible.  profiles/r05_marcher_split_path.md)
@@ -1074,7 +1076,7 @@ __global__ __launch_bounds__(256, WG) void k4_shade_kernel(const MarchParams P) 
                     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                     for (int c = 0; c < 8; ++c) {
-                        const float4 q = (P.debug & 1) ? make_float4(cw[c], 0.5f, 0.25f, 1.f) : *reinterpret_cast<const float4*>(P.k0 + (size_t)cidx[c] * P.CP + g);
+                        const float4 q = (P.ablate & 1) ? make_float4(cw[c], 0.5f, 0.25f, 1.f) : *reinterpret_cast<const float4*>(P.k0 + (size_t)cidx[c] * P.CP + g);
                         v.x += q.x * cw[c]; v.y += q.y * cw[c]; v.z += q.z * cw[c]; v.w += q.w * cw[c];
                     }
                     const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -1140,11 +1142,11 @@ __global__ __launch_bounds__(256, WG) void k4_shade_kernel(const MarchParams P) 
                 constexpr int NT2 = ARITH == 3 ? 3 : 2, NT1 = ARITH == 3 ? 3 : K4_B2_L1_TERMS;
                 if constexpr (K4_MLP_PAIR && W == 64 && NHID == 1) {
                     // a full batch of the LLFF shape: both tiles through one software pipeline (same bits); anything else one tile at a time
-                    if (P.k1p == 16 && nproc > 32 && !(P.debug & 2)) mlp_pair64<NT1, NT2>(wl, fs, lane, half, l0, l1, l2 K4_TPASS);
-                    else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, P.k1p, lane, half, P.debug, nproc, l0, l1, l2 K4_TPASS);
-                } else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, P.k1p, lane, half, P.debug, nproc, l0, l1, l2 K4_TPASS);
+                    if (P.k1p == 16 && nproc > 32 && !(P.ablate & 2)) mlp_pair64<NT1, NT2>(wl, fs, lane, half, l0, l1, l2 K4_TPASS);
+                    else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, P.k1p, lane, half, P.ablate, nproc, l0, l1, l2 K4_TPASS);
+                } else mlp_mfma_bx<W, NHID, NT1, NT2>(wl, fs, P.k1p, lane, half, P.ablate, nproc, l0, l1, l2 K4_TPASS);
             }
-            else mlp_mfma<W, NHID>(wl, feat, P.k1p, lane, half, P.debug, l0, l1, l2);
+            else mlp_mfma<W, NHID>(wl, feat, P.k1p, lane, half, P.ablate, l0, l1, l2);
             o0 = l0 + dif0; o1 = l1 + dif1; o2 = l2 + dif2;            // rgb_logit + k0_diffuse (lib/dvgo.py:412)
             __builtin_amdgcn_wave_barrier();
         }
@@ -1166,7 +1168,7 @@ __global__ __launch_bounds__(256, WG) void k4_shade_kernel(const MarchParams P) 
             }
             f0 &= 0x7fffffffu; f1 &= 0x7fffffffu; f2 &= 0x7fffffffu;
         }
-        if (lact && !(P.debug & 512)) {                                  // (512: ablation, no per-ray sums)
+        if (lact && !(P.ablate & 512)) {                                 // (512: ablation, no per-ray sums)
             k4_lds_add(&acc[rl * 2 + 0], (unsigned long long)f0 | ((unsigned long long)f1 << 32));
             k4_lds_add(&acc[rl * 2 + 1], (unsigned long long)f2 | ((unsigned long long)f3 << 32));
         }
@@ -1226,11 +1228,11 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
         // FAST: the LLFF configuration (see k4_geom3_kernel); anything else -- DVGO, the counting instantiation, a split scene, stepsize != 1,
         // a scene without the occupancy summary, more than K4_TKTAB samples, any ablation bit the kernel reads -- takes the general instantiation
         const bool gfast = MODE == MODE_MPI && !P.counters && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr &&
-                           P.Z >= 2 && P.n_samples <= K4_TKTAB && (P.debug & K4_GEOM_DEBUG_BITS) == 0 && !k4_env().no_fast_geom;
+                           P.Z >= 2 && P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom;
 #ifdef K4_GEOM_TIMING
         if (P.counters) { MarchParams Q = P; Q.timing = P.counters + 8; Q.counters = nullptr;       // the instantiation the render path would take
                           const bool tfast = MODE == MODE_MPI && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr && P.Z >= 2 &&
-                                             P.n_samples <= K4_TKTAB && (P.debug & K4_GEOM_DEBUG_BITS) == 0 && !k4_env().no_fast_geom;
+                                             P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom;
                           if (tfast) hipLaunchKernelGGL((k4_geom3_kernel<MODE_MPI, false, 5, true>), dim3((unsigned)nwg * 4), block, 0, st, Q);
                           else hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q); } else
 #endif
@@ -1357,7 +1359,7 @@ static int fill_common(MarchParams& P, const float* rays_o, const float* rays_d,
     P.qhead = (int*)((char*)workspace + L.qhead);
     P.jobs = (int2*)((char*)workspace + L.jobs);
     P.n_bundles = (int)nb;
-    P.debug = k4_env().debug; P.serp = 1;
+    P.ablate = k4_env().ablate; P.serp = 1;
     // XCD bands of the geometry kernel: ONE row of 16x16-pixel workgroup tiles (x 4 bundles) per band, dealt round-robin to
     // the 8 XCDs.  One contiguous band per XCD (0) left the XCDs 0.61..1.31 of the mean work on the LLFF frames -- the kernel ran at
     // the pace of the heaviest eighth of the image.
@@ -1381,11 +1383,6 @@ static void set_depth_fx(MarchParams& P, int max_steps) {
 
 extern "C" int k4_abi_version(void) { return K4_ABI_VERSION; }
 
-static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
-static const K4Env g_k4_env = {        // namespace-scope constant: initialised while the library is loaded, immutable afterwards
-    env_int("K4_GEOM_SKIP", 1), env_int("K4_DEBUG", 0), env_int("K4_SR_DEBUG", 0), (env_int("K4_DEBUG", 0) & 1024) != 0,
-    (env_int("K4_DEBUG", 0) & 16384) != 0};
-const K4Env& k4_env() { return g_k4_env; }
 int k4_num_cus() {
     static int n_cu[K4_MAX_DEVICES];
     const int dev = k4_device_ordinal();
@@ -1425,7 +1422,7 @@ extern "C" int k4_march_mpi_fwd(const float* rays_o, const float* rays_d, const 
     }
     P.n_samples = n_samples; P.depth_n = n_samples; P.nsm1 = (float)(n_samples - 1);
     if (grid->depth_split < 0 || grid->depth_split % 64 != 0 || grid->depth_split >= n_samples) return K4_ERR_BAD_ARG;
-    P.split_k = k4_env().debug & 2048 ? 0 : grid->depth_split;                               // (K4_DEBUG & 2048: single launch whatever the descriptor says, A/B)
+    P.split_k = k4_env().single_launch ? 0 : grid->depth_split;                               // (K4_DEBUG & 2048: single launch whatever the descriptor says, A/B)
     set_depth_fx(P, n_samples);
     P.shift = 0.f;                                                                            // lib/dmpigo.py:261
     P.interval = interval; P.thres = fast_color_thres; P.bg = bg;

@@ -23,17 +23,17 @@ struct MlpLayout {
 
 // rgbnet on the matrix cores: logits[3] of the sample owned by this lane, features read from LDS feat[K1P][64].
 template <int W, int NHID>
-__device__ __forceinline__ void mlp_mfma(const float* wl, const float* feat, int k1p_, int lane, int half, int debug_,
+__device__ __forceinline__ void mlp_mfma(const float* wl, const float* feat, int k1p_, int lane, int half, int ablate_,
                                          float& out0, float& out1, float& out2) {
     constexpr int NB = W / 32;
     typedef MlpLayout<W, NHID> ML;
-    const struct { int k1p; int debug; } P = {k1p_, debug_};
+    const struct { int k1p; int ablate; } P = {k1p_, ablate_};
     // ---------------- layer 1: H1^T[j][s] = sum_k W1ext[j][k] * X[k][s]  ----------------
     f32x16 h1[NB][2];
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb) { h1[mb][0] = (f32x16)(0.f); h1[mb][1] = (f32x16)(0.f); }
     const float* const w1a = wl + ML::w1a(P.k1p);
-    const int ksteps = (P.debug & 2) ? 0 : (P.k1p >> 1);
+    const int ksteps = (P.ablate & 2) ? 0 : (P.k1p >> 1);
     for (int kk = 0; kk < ksteps; ++kk) {
         const float b0 = feat[(2 * kk + half) * 64 + (lane & 31)];
         const float b1 = feat[(2 * kk + half) * 64 + 32 + (lane & 31)];
@@ -52,7 +52,7 @@ __device__ __forceinline__ void mlp_mfma(const float* wl, const float* feat, int
     // partial output sums of the two 32-sample tiles (this lane: neurons row(r,half) of each block)
     float pt[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
     const float* const wot = wl + ML::wot(P.k1p);
-    if (NHID == 1 && !(P.debug & 2)) {
+    if (NHID == 1 && !(P.ablate & 2)) {
         const float* const w2a = wl + ML::w2a(P.k1p);
         const float* const b2a = wl + ML::b2a(P.k1p);
 #pragma unroll 1
@@ -288,7 +288,7 @@ struct RegFeat {
 // blocks of a layer are taken two at a time, side by side (independent accumulators: consecutive MFMAs never depend on each other);
 // width 128 = two such passes per layer, so that at most 2 x 16 accumulators are live beside the split hidden activations.
 template <int W, int NHID, int NT1, int NT2, class FS, bool TILE0_ONLY = false>      // TILE0_ONLY: the caller guarantees nproc <= 32
-__device__ __forceinline__ void mlp_mfma_bx(const float* ws, FS& fs, int k1p, int lane, int half, int debug, int nproc,
+__device__ __forceinline__ void mlp_mfma_bx(const float* ws, FS& fs, int k1p, int lane, int half, int ablate, int nproc,
                                             float& out0, float& out1, float& out2 K4_TARGS) {
     constexpr int NB = W / 32;
     constexpr int KB2 = W / 16;
@@ -296,7 +296,7 @@ __device__ __forceinline__ void mlp_mfma_bx(const float* ws, FS& fs, int k1p, in
     constexpr int PB = NB >= 2 ? 2 : 1;                   // blocks per pass
     typedef MlpLayoutB3<W, NHID, NT1, NT2> ML;
     const int kb1n = ML::kb1(k1p);
-    const int kb1 = (debug & 2) ? 0 : kb1n;
+    const int kb1 = (ablate & 2) ? 0 : kb1n;
     const uint4* const w1s = reinterpret_cast<const uint4*>(ws + ML::w1s(k1p));
     const uint4* const w2s = reinterpret_cast<const uint4*>(ws + ML::w2s(k1p));
     const float* const b2s = ws + ML::b2s(k1p);
@@ -354,7 +354,7 @@ __device__ __forceinline__ void mlp_mfma_bx(const float* ws, FS& fs, int k1p, in
                 pt2 = fmaf(wo.z, a0, pt2);
             }
         };
-        if (NHID == 1 && !(debug & 2)) {
+        if (NHID == 1 && !(ablate & 2)) {
             // relu + split of this tile's hidden activations once
             uint4 hs[KB2][NT2];
 #pragma unroll

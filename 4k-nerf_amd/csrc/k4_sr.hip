@@ -42,7 +42,8 @@ struct ConvParams {
     const float* res; int res_stride; float res_scale;
     const float* modx; int mod_stride;
     int tiles_x, tiles_y;
-    int debug;           // K4_SR_DEBUG ablation bits of the v2 3x3 kernel (profiling only, WRONG results; 0 in production): 2 = no epilogue stores,
+    int ablate;          // K4Env.sr_ablate: K4_SR_DEBUG ablation bits of the v2 3x3 kernel (profiling only, WRONG results; always 0 in the product build, k4_env.h; the kernel tests
+                         // the field itself, not K4_ABL: folded, the bf16x6 frame was 3 % slower, profiles/ablate_build.md): 2 = no epilogue stores,
                          // 4 = no MFMA phase, 8 = no split / LDS stores after the first chunk, 16 = no activation loads after the first chunk
 };
 
@@ -798,7 +799,7 @@ __global__ __launch_bounds__(256, (F16 ? (RPW == 2 ? K4_V2_MINWG_F16 : 2) : NTER
                 tcur = tnew;
                 sexp = tnew - bch;                                                         // <= enat: the chunk fits fp16
                 const float sc = ldexpf(1.f, sexp);
-                if (!(P.debug & 8) || ch == 0)
+                if (!(P.ablate & 8) || ch == 0)
 #pragma unroll
                 for (int i = 0; i < IN_PER; ++i) {
                     uint2 t0, t1;
@@ -825,7 +826,7 @@ __global__ __launch_bounds__(256, (F16 ? (RPW == 2 ? K4_V2_MINWG_F16 : 2) : NTER
             __syncthreads();
             K4_SR_TSTAMP(2);                             // barrier A
             // next staging unit: the next chunk of this tile (its loads fly during the MFMAs below)
-            if (ch + 1 < nchunks && !(P.debug & 16)) {
+            if (ch + 1 < nchunks && !(P.ablate & 16)) {
                 K4_V2_LOADRAW(ch + 1);
                 if constexpr (WL) K4_V2_LOADW(ch + 1);
             }
@@ -840,7 +841,7 @@ __global__ __launch_bounds__(256, (F16 ? (RPW == 2 ? K4_V2_MINWG_F16 : 2) : NTER
             K4_V2_READA(abuf[0], 0);
             if (AD == 2) K4_V2_READA(abuf[1], 1);
             K4_SR_TSTAMP(3);                             // next chunk's loads issued, first fragments requested
-            if (!(P.debug & 4))
+            if (!(P.ablate & 4))
 #pragma unroll
             for (int u = 0; u < NSUB; ++u) {
                 const int t = u / RPW, r = u % RPW;
@@ -886,7 +887,7 @@ __global__ __launch_bounds__(256, (F16 ? (RPW == 2 ? K4_V2_MINWG_F16 : 2) : NTER
             K4_SR_TSTAMP(6);                             // barrier B
         }
         // ---- epilogue of tile T: lane holds output channel nb*32 + l31 of pixels x0 + row(reg, half) in rows y0 + wv*4 + r ----
-        if (P.debug & 2) {
+        if (P.ablate & 2) {
             float sum_ = 0.f;
 #pragma unroll
             for (int j = 0; j < NBK; ++j)
@@ -1118,7 +1119,7 @@ __global__ __launch_bounds__(256) void k4_conv_ks_kernel(const ConvMulti M) {
 static int launch_conv_b6v2(ConvMulti& M, hipStream_t st) {
     const int nbc = (M.base.cout + 31) / 32;
     // K4_CONV_SMALL: one window, plain 3-term arithmetic, an image small enough that one-row workgroups do not exceed four per CU
-    if ((M.base.flags & K4_CONV_SMALL) && M.n == 1 && !(M.base.flags & (K4_ARITH_2TERM | K4_ARITH_F16X3 | K4_PRE_UPSAMPLE2X)) && !(k4_env().sr_debug & 2048)) {
+    if ((M.base.flags & K4_CONV_SMALL) && M.n == 1 && !(M.base.flags & (K4_ARITH_2TERM | K4_ARITH_F16X3 | K4_PRE_UPSAMPLE2X)) && !k4_env().row_kernel) {
         const long long wgs = (long long)((M.W[0] + TILE_W - 1) / TILE_W) * M.H[0] * nbc;
         if (wgs <= 4ll * k4_num_cus() && (long long)M.H[0] * M.W[0] * M.base.cin_stride <= 0x7fffffffLL) {
             M.tiles_x[0] = (M.W[0] + TILE_W - 1) / TILE_W;
@@ -1163,8 +1164,8 @@ static int launch_conv_b6v2(ConvMulti& M, hipStream_t st) {
         total = count(4 * rpw);
     }
     M.total = total;
-    if (k4_env().sr_debug & 1) M.base.cin_stride = 0;        // profiling only (WRONG results): every pixel reads the same 64 bytes -- the kernel without memory traffic
-    M.base.debug = k4_env().sr_debug;
+    if (K4_ABL(k4_env().sr_ablate, 1)) M.base.cin_stride = 0;        // ablation (WRONG results): every pixel reads the same 64 bytes -- the kernel without memory traffic
+    M.base.ablate = k4_env().sr_ablate;
     const dim3 grid((unsigned)total), block(256);
 #define K4_V2_LAUNCH(...) do { \
         if (rpw == 1) hipLaunchKernelGGL((k4_conv_b6v2_kernel<1, __VA_ARGS__>), grid, block, 0, st, M); \
@@ -1977,8 +1978,8 @@ static int sft_multi(const k4_sft_job* jobs, int32_t n_jobs, int32_t cond_stride
     P.vec4 = ((x_stride | y_stride | (any_res ? res_stride : 0)) & 3) == 0 && (align & 15) == 0;
     const dim3 grid((unsigned)total), block(256);
     if (arith == K4_SFT_ARITH_BF16X6) {
-        // the pipelined form addresses through 32-bit buffer offsets: 16-byte rows, every image below 2 GB (K4_SR_DEBUG bit 5: A/B)
-        const bool piped = P.vec4 && max_bytes < (1ll << 31) && !(k4_env().sr_debug & 32);
+        // the pipelined form addresses through 32-bit buffer offsets: 16-byte rows, every image below 2 GB (K4_SR_DEBUG & 32: the unpipelined kernel, A/B)
+        const bool piped = P.vec4 && max_bytes < (1ll << 31) && !k4_env().sft_unpiped;
         if (out_scale != 0.f) {                                      // p16 output: the pipelined kernel only (aligned rows, images below 2 GB), no residual
             if (!piped || any_res || (y_stride & 15)) return K4_ERR_UNSUPPORTED;
             for (int g = 0; g < n_jobs; ++g) if (((size_t)jobs[g].y) & 63) return K4_ERR_BAD_ARG;       // the slice starts on a 16-channel chunk

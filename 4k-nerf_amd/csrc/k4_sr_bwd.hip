@@ -280,7 +280,7 @@ static int wgrad_launch(const float* x, int32_t cin, int32_t x_stride, const flo
     P.ks = ksize; P.H = H; P.W = W; P.dw = dw; P.db = dbias;
     P.ci_blocks = (cin + 31) / 32; P.co_blocks = (cout + 31) / 32; P.bands = (H + K4_WG_BAND - 1) / K4_WG_BAND;
     if (zero_floats > 0) wg_zero(dw, zero_floats, (hipStream_t)stream);                                                 // split-K partial sums are ADDED
-    if (ksize == 3 && !(k4_env().sr_debug & 4096)) {
+    if (ksize == 3 && !k4_env().wgrad_per_tap) {
         // units per wave: as many workgroups as ~3 per CU allow, at least 4 units (the tile reduction amortises over them)
         P.units = H * ((W + 15) / 16);
         const int want_groups = 768 / (P.ci_blocks * P.co_blocks) > 0 ? 768 / (P.ci_blocks * P.co_blocks) : 1;

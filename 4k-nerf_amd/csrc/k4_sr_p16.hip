@@ -46,7 +46,7 @@ struct P16Conv {
     // SFT epilogue (k4_conv3x3_p16_sft_multi): the layer's result v goes through the NEXT SFTLayer before it is stored pre-split into y2
     const float* cond[K4_MAX_JOBS]; void* y2[K4_MAX_JOBS];
     const void* w_sfe; int cond_stride, y2_stride; float cond_scale, sft_slope;
-    int debug;               // K4_SR_DEBUG ablation bits (profiling only, WRONG results; 0 in production): 64 = activation DMA for chunk 0 only, 128 = weight DMA for
+    int ablate;              // K4Env.sr_ablate: K4_SR_DEBUG ablation bits (profiling only, WRONG results; always 0 in the product build, k4_env.h): 64 = activation DMA for chunk 0 only, 128 = weight DMA for
                              // chunk 0 only, 256 = no MFMAs, 512 = every pixel reads pixel 0 (no HBM traffic)
 };
 
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void k4_conv_p16_kernel(const P16Conv M) {
             const int row = p / P16_COLS, col = p - row * P16_COLS;
             const int gy = y0 - 1 + row, gx = x0 - 1 + col;
             const bool inside = item < P16_ACT_ITEMS && gy >= 0 && gy < srcH && gx >= 0 && gx < srcW;
-            aoff[i] = inside ? (unsigned)(((M.debug & 512) ? 0 : (gy * srcW + gx) * M.cin_stride * 4) + ((j ^ ((col >> 2) & 3)) << 4)) : P16_OOB;
+            aoff[i] = inside ? (unsigned)((K4_ABL(M.ablate, 512) ? 0 : (gy * srcW + gx) * M.cin_stride * 4) + ((j ^ ((col >> 2) & 3)) << 4)) : P16_OOB;
         }
     }
     const unsigned woff = (unsigned)(lane * 16);
@@ -149,12 +149,12 @@ __global__ __launch_bounds__(256, 2) void k4_conv_p16_kernel(const P16Conv M) {
         const int aso_ = (CH) * 64; \
         _Pragma("unroll") for (int i_ = 0; i_ < WW; ++i_) { \
             const int k_ = wi + NISS * i_; \
-            if (k_ < W_NI && (!(M.debug & 128) || (CH) == 0)) \
+            if (k_ < W_NI && (!K4_ABL(M.ablate, 128) || (CH) == 0)) \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)((WB) + k_ * 1024), 16, (int)woff, wso_ + k_ * 1024, 0, 0); \
         } \
         _Pragma("unroll") for (int i_ = 0; i_ < AW; ++i_) { \
             const int k_ = wi + NISS * i_; \
-            if ((k_ < P16_ACT_INSTR - 1 || (k_ == P16_ACT_INSTR - 1 && lane < P16_ACT_ITEMS - (P16_ACT_INSTR - 1) * 64)) && (!(M.debug & 64) || (CH) == 0)) \
+            if ((k_ < P16_ACT_INSTR - 1 || (k_ == P16_ACT_INSTR - 1 && lane < P16_ACT_ITEMS - (P16_ACT_INSTR - 1) * 64)) && (!K4_ABL(M.ablate, 64) || (CH) == 0)) \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)((AB) + k_ * 1024), 16, (int)aoff[i_], aso_, 0, 0); \
         } } } while (0)
 
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void k4_conv_p16_kernel(const P16Conv M) {
         P16_RDW(wa[0], WB, 0); \
         P16_RDX(xb[0], AB, 0); \
         P16_RDX(xb[1], AB, 1); \
-        if (!(M.debug & 256)) \
+        if (!K4_ABL(M.ablate, 256)) \
         _Pragma("unroll") for (int u = 0; u < NSUB; ++u) { \
             const int t = u >> 1, r = u & 1; \
             if (r == 0 && t + 1 < NTAP) P16_RDW(wa[(t + 1) & 1], WB, t + 1); \
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void k4_conv_p16_kernel(const P16Conv M) {
         p16_u32x4 ww[2][2][2][2], xx[2][3][2];                   /* [buffer][px][b][term], [buffer][column][term] */ \
         P16_RDW_UP(ww[0], WB, 0); \
         P16_RDX_UP(xx[0], AB, 0); \
-        if (!(M.debug & 256)) \
+        if (!K4_ABL(M.ablate, 256)) \
         _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {       /* stage s = (a = s >> 1, r = s & 1) */ \
             const int a_ = s_ >> 1, r_ = s_ & 1; \
             if (s_ == 1) P16_RDW_UP(ww[1], WB, 1); \
@@ -555,7 +555,7 @@ static int conv3x3_p16(const k4_conv_job* jobs, const k4_conv_sft_job* sjobs, in
     if ((((size_t)w_p16) & 15) || (((size_t)bias) & 15)) return K4_ERR_BAD_ARG;
     P16Conv M{};
     M.n = n_jobs; M.cin = cin; M.cin_stride = cin_stride; M.w = w_p16; M.bias = bias; M.cout = cout; M.cout_stride = cout_stride;
-    M.flags = flags; M.slope = slope; M.res_stride = res_stride; M.res_scale = res_scale; M.out_scale = out_scale; M.overflow = overflow; M.debug = k4_env().sr_debug;
+    M.flags = flags; M.slope = slope; M.res_stride = res_stride; M.res_scale = res_scale; M.out_scale = out_scale; M.overflow = overflow; M.ablate = k4_env().sr_ablate;
     M.w_sfe = w_sfe; M.cond_stride = cond_stride; M.y2_stride = y2_stride; M.cond_scale = cond_scale; M.sft_slope = sft_slope;
     const int nbc = cout / 32;
     int total = 0;

@@ -164,10 +164,12 @@ int k4_mlp_b2_layer1_terms(void);    /* NT1 of the default section: 2 (3 in A/B 
  *                  transmittance scan: what a depth-ordered geometry stage could skip), 0, 0, 0}, ACCUMULATED
  *                  (caller zeroes) -- the counts SURVEY 8(d)'s algorithmic-bytes formula needs.
  * Both kernels have a FAST instantiation for the LLFF configuration (shape fixed at compile time, same expression trees, same bits as
- * their general paths).  K4_DEBUG bits (environment, read once at load) that keep exact results: 1024 = general shading path,
- * 2048 = one geometry launch whatever grid->depth_split says, 16384 = general geometry path (k4_march_mpi_fwd with interval == 1,
- * fast_color_thres > 0, depth_split == 0, an occupancy summary, n_samples <= 256 and no counters takes the FAST one otherwise).
- * Every other bit is a profiling ablation with WRONG results.
+ * their general paths).  K4_DEBUG bits (environment, read once at load) that keep exact results and that every build honours: 1024 =
+ * general shading path, 2048 = one geometry launch whatever grid->depth_split says, 16384 = general geometry path (k4_march_mpi_fwd with
+ * interval == 1, fast_color_thres > 0, depth_split == 0, an occupancy summary, n_samples <= 256 and no counters takes the FAST one
+ * otherwise).  The other bits the library knows (K4_DEBUG & 12979, K4_SR_DEBUG & 991) are profiling ablations with WRONG results: they exist
+ * only in a library built with -DK4_ABLATE (build.py --tag ablate -DK4_ABLATE); the default library ignores them and says so on stderr
+ * while it loads (csrc/k4_env.h).
  * ------------------------------------------------------------------------------------------- */
 int64_t k4_march_workspace_bytes(int64_t n_rays, int32_t img_w, int32_t max_steps);
 

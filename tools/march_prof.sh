@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel stats of the isolated marcher call under a set of env knobs: bash tools/march_prof.sh <tag> [ENV=VAL ...]  (GPU box)
 TAG=$1; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/r05_march
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
