@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 22
+K4_ABI_VERSION = 23
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -284,6 +284,10 @@ _EXTRA_SIGS = {
     'k4_vgg_gram_workspace_bytes': ([_I32, _I32], C.c_int64),
     'k4_vgg_gram': ([_P, _I32, _I32, _P, _I64, _P, _P], C.c_int),
     'k4_vgg_gram_bwd_pack': ([_P, _I32, _I32, _F, _P, _P, _P], C.c_int),
+    'k4_lpips_workspace_bytes': ([_I64], C.c_int64),
+    'k4_lpips_head': ([_P, _I64, _I32, _P, _P, _P, _I32, _P], C.c_int),
+    'k4_lpips_total': ([_P, _I32, _P, _P], C.c_int),
+    'k4_lpips_check_frame': ([_I32, _I32], C.c_int),
     'k4_frame_metrics_workspace_bytes': ([_I32, _I32, _I32], C.c_int64),
     'k4_tensorf_sample': ([_P] * 7 + [_I32] * 6 + [_P, _P, _P, _I64, _P, _P], C.c_int),
     'k4_tensorf_sample_backward': ([_P] * 8 + [_I32] * 6 + [_P, _P, _P, _I64] + [_P] * 8, C.c_int),

@@ -6,7 +6,8 @@
 //                        of k4_disc_conv_s2, with the correction products in an accumulator of their own: VG_MFMA6).  A workgroup owns MT tiles of 4 x 8 output pixels x 32*NT output channels; its four (or eight) waves split
 //                        the reduction (tap, 16-channel chunk) round-robin and are summed through LDS in wave order -- conv5_x is 16 x 16 pixels with
 //                        K = 4608.  A lane's 16 accumulator registers hold, for one channel, a 4-row x 4-column patch of the tile, so the 2x2 max pool
-//                        that follows a layer is taken in registers in the epilogue.  Epilogue, forward: bias, the pre-ReLU copy of a tapped layer, ReLU,
+//                        that follows a layer is taken in registers in the epilogue.  Any H, W >= 1: a partial tile's pixels outside the image gather zeros and
+//                        store nothing, and the pool is floor-mode (odd H or W: the last row or column is in no window).  Epilogue, forward: bias, the pre-ReLU copy of a tapped layer, ReLU,
 //                        the pooled image.  Epilogue, input gradient: the ReLU mask of the producing layer (saved activation > 0) and an added seed.
 //   k4_vgg_conv1_1       the first layer (3 planar input channels, normalisation (x - mean) / std in the load) and its input gradient (1 / std in the
 //                        store, planar): 27-term sums in plain fp32, one fixed order.
@@ -212,7 +213,9 @@ extern "C" int k4_vgg_conv3x3(const float* x, int32_t cin, int32_t H, int32_t W,
     if (mode == K4_VGG_CONV_FWD && (mask || add)) return K4_ERR_BAD_ARG;
     if (mode == K4_VGG_CONV_DGRAD && (bias || y_pre || y_pool || relu)) return K4_ERR_BAD_ARG;
     if (cin % 16 != 0 || ((uintptr_t)x & 15) != 0) return K4_ERR_UNSUPPORTED;                                   // 16-byte activation loads
-    if (y_pool && ((H & 1) || (W & 1) || !relu)) return K4_ERR_UNSUPPORTED;
+    // floor mode (torchvision's MaxPool2d(2, 2)): an odd last row or column belongs to no window.  The epilogue bounds a window by qy < H / 2 and qx < W / 2,
+    // so every window it stores lies inside the image; an image with H or W below 2 has no window at all and is refused
+    if (y_pool && (H < 2 || W < 2 || !relu)) return K4_ERR_UNSUPPORTED;
     if ((int64_t)H * W * batch > (1 << 26)) return K4_ERR_UNSUPPORTED;
     VggConv P{};
     P.x = x; P.cin = cin; P.H = H; P.W = W; P.B = batch;

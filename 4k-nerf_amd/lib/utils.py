@@ -3,7 +3,9 @@
 DVGO/MPI checkpoints: ``{'global_step', 'model_kwargs', 'model_state_dict', 'optimizer_state_dict'}``
 (run_sr.py:1173-1178).  Only what the render / training-step path needs is restated.  Frame evaluation: ``rgb_ssim`` with the
 reference's signature (lib/utils.py:88-134) and ``frame_metrics`` (MSE, PSNR and SSIM of a frame pair in one pass) run on the device
-(csrc/k4_metric.hip); LPIPS is out of scope (its linear-layer weights cannot be pinned to their upstream).
+(csrc/k4_metric.hip).  LPIPS: ``init_lpips`` / ``rgb_lpips`` with the reference's signatures (lib/utils.py:137-149) and ``frame_lpips`` for device
+frames run lib/lpips.LPIPS (VGG only) on csrc/k4_vgg.hip and csrc/k4_lpips.hip.  Nothing is fetched: the caller registers the weights with
+``load_lpips_weights`` first, and an unregistered metric raises ``NotImplementedError``.
 """
 import numpy as np
 import torch
@@ -204,3 +206,73 @@ def frame_metrics(pred, gt, max_val=1.0, clamp_pred=False, return_map=False):
     if return_map:
         out['ssim_map'] = ssim_map
     return out
+
+
+# ---- LPIPS (lib/lpips.py on csrc/k4_vgg.hip + csrc/k4_lpips.hip) ------------------------------------------------------
+__LPIPS__ = {}                  # net_name -> module, as lib/utils.py:137
+_LPIPS_WEIGHTS = None           # (state dict, lin state dict or None) registered by load_lpips_weights
+
+
+def load_lpips_weights(obj):
+    """Register the LPIPS-VGG weights for this process: a state dict with the keys of lib/lpips.LPIPS, a ``(torchvision vgg16 state dict, lin state
+    dict)`` pair (``lin<k>.model.1.weight`` or ``lins.<k>.model.1.weight``: the `lpips` package's weights/v0.1/vgg.pth), a path to a ``torch.save``d one
+    of those, or ``None`` to clear.  Nothing is fetched.  Missing layers raise ``KeyError`` and wrong shapes ``ValueError`` here, not at the first frame."""
+    global _LPIPS_WEIGHTS
+    __LPIPS__.clear()
+    if obj is None:
+        _LPIPS_WEIGHTS = None
+        return
+    if not isinstance(obj, (dict, tuple, list)):
+        obj = torch.load(obj, map_location='cpu', weights_only=True)
+    sd, lin = (obj[0], obj[1]) if isinstance(obj, (tuple, list)) else (obj, None)
+    from . import lpips
+    lpips.LPIPS(net='vgg', version='0.1', verbose=False).load_lpips_state_dict(sd, lin)
+    _LPIPS_WEIGHTS = (sd, lin)
+
+
+def lpips_weights_registered():
+    return _LPIPS_WEIGHTS is not None
+
+
+LPIPS_ALEX_MISSING = ("LPIPS (alex) is not provided: the `lpips` package's AlexNet backbone needs kernels this package does not have "
+                      "(only net_name='vgg', eval_lpips_vgg)")
+LPIPS_WEIGHTS_MISSING = ("LPIPS (vgg) needs the `lpips` package's weights, which are never fetched: register them first with "
+                         'lib.utils.load_lpips_weights(state dict | (vgg16 state dict, lin state dict) | path)')
+
+
+def init_lpips(net_name, device):
+    """lib/utils.py:138-142: the module is built from the weights registered with ``load_lpips_weights``."""
+    assert net_name in ['alex', 'vgg']
+    if net_name == 'alex':
+        raise NotImplementedError(LPIPS_ALEX_MISSING)
+    if _LPIPS_WEIGHTS is None:
+        raise NotImplementedError(LPIPS_WEIGHTS_MISSING)
+    from . import lpips
+    print(f'init_lpips: lpips_{net_name}')
+    return lpips.LPIPS(net=net_name, version='0.1', verbose=False).load_lpips_state_dict(*_LPIPS_WEIGHTS).eval().to(device)
+
+
+def rgb_lpips(np_gt, np_im, net_name, device):
+    """lib/utils.py:144-149: numpy [H,W,3] frames in [0, 1] -> Python float (one host synchronisation, the reference's ``.item()``)."""
+    if net_name not in __LPIPS__:
+        __LPIPS__[net_name] = init_lpips(net_name, device)
+    gt = torch.from_numpy(np_gt).permute([2, 0, 1]).contiguous().to(device)
+    im = torch.from_numpy(np_im).permute([2, 0, 1]).contiguous().to(device)
+    return __LPIPS__[net_name](gt, im, normalize=True).item()
+
+
+def frame_lpips(pred, gt, clamp_pred=False):
+    """The device form of ``rgb_lpips(gt, pred, 'vgg', device)``: frames are device float32 tensors, channel-last [H,W,3] (the marcher's) or planar
+    [3,H,W] / [1,3,H,W] (the decoder's), in [0, 1]; clamp_pred clamps `pred` first (run_sr.py:1131).  Returns a device float32 scalar without a
+    host synchronisation."""
+    def planar(img, what):
+        v, H, W, _, _ = _metric_image(img, what)
+        if tuple(v.shape) == (H, W, 3) and not (img.dim() == 4):
+            v = v.permute(2, 0, 1)
+        return v.contiguous()
+    a, b = planar(pred, 'pred'), planar(gt, 'gt')
+    if clamp_pred:
+        a = a.clamp(0, 1)
+    if 'vgg' not in __LPIPS__:
+        __LPIPS__['vgg'] = init_lpips('vgg', a.device)
+    return __LPIPS__['vgg'](b, a, normalize=True).reshape(())

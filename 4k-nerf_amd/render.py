@@ -45,16 +45,17 @@ def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs,
                       arr_index=None, img_enc=None):
     '''Render images for the given viewpoints; run evaluation if gt given.'''
     assert len(render_poses) == len(HW) and len(HW) == len(Ks)
-    if eval_lpips_alex or eval_lpips_vgg:
-        raise NotImplementedError("LPIPS evaluation needs the `lpips` package's linear-layer weights, which are not available: "
-                                  'nothing of it could be pinned to its upstream (SSIM: eval_ssim=True)')
+    if eval_lpips_alex:             # on entry, before the model is touched: nothing is fetched, so a metric that cannot run raises
+        raise NotImplementedError(utils.LPIPS_ALEX_MISSING)
+    if eval_lpips_vgg and not utils.lpips_weights_registered():
+        raise NotImplementedError(utils.LPIPS_WEIGHTS_MISSING)
     if render_factor != 0:
         HW = np.copy(HW)
         Ks = np.copy(Ks)
         HW = (HW / render_factor).astype(int)
         Ks[:, :2, :3] /= render_factor
     rgbs, rgb_features, depths, bgmaps, psnrs, viewdirs_all = [], [], [], [], [], []
-    ssims = []
+    ssims, lpips_vgg = [], []
     for i, c2w in enumerate(render_poses):
         H, W = int(HW[i][0]), int(HW[i][1])
         K = Ks[i]
@@ -75,8 +76,13 @@ def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs,
             if eval_ssim:       # run_sr.py:146-147 on the device: the frame is clamped in the kernel's load, the value stays there until the loop is done
                 gt = gt_imgs[i] if isinstance(gt_imgs[i], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_imgs[i]))
                 ssims.append(utils.frame_metrics(res['rgb_marched'], gt.to(dev), max_val=1, clamp_pred=True)['ssim'])
+            if eval_lpips_vgg:  # run_sr.py:150-151 on the device, the values held there until the loop is done
+                gt = gt_imgs[i] if isinstance(gt_imgs[i], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(gt_imgs[i]))
+                lpips_vgg.append(utils.frame_lpips(res['rgb_marched'], gt.to(dev), clamp_pred=True))
     if len(psnrs) and eval_ssim:
         print('Testing ssim', np.mean([float(s) for s in ssims]), '(avg)')          # run_sr.py:155
+    if len(psnrs) and eval_lpips_vgg:
+        print('Testing lpips (vgg)', np.mean([float(v) for v in lpips_vgg]), '(avg)')          # run_sr.py:157
     if render_video_flipy:
         for i in range(len(rgbs)):
             rgbs[i], depths[i], bgmaps[i] = np.flip(rgbs[i], 0), np.flip(depths[i], 0), np.flip(bgmaps[i], 0)

@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      22      /* 22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      23      /* 23: LPIPS-VGG frame scoring (csrc/k4_lpips.hip): k4_lpips_head(+_workspace_bytes), k4_lpips_total, k4_lpips_check_frame; k4_vgg_conv3x3 takes any H, W >= 1 and pools in floor mode;  22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -880,7 +880,8 @@ int k4_gan_loss_bwd(const float* logits, int64_t n, int32_t target_is_real, floa
  *
  * k4_vgg_conv3x3, by `mode` (ksize 3: pad 1; ksize 1: a per-pixel product):
  *   K4_VGG_CONV_FWD    v = bias + sum x[p - 1 + d][ci] W[co][ci][d];  y_pre (NULL: not kept) = v, the tap of a `convK_J` layer;  y (NULL: not kept) = relu ? max(v, 0) : v;
- *                      y_pool (NULL: none; H, W even, relu set) = the 2x2 stride-2 max pool of y.  w_split = k4_vgg_pack_weight(..., K4_VGG_CONV_FWD)
+ *                      y_pool (NULL: none; relu set; H, W >= 2) [batch][H/2][W/2][cout] = the 2x2 stride-2 max pool of y in floor mode (torchvision's MaxPool2d(2, 2):
+ *                      for odd H or W the last row or column is dropped).  Any H, W >= 1 with H * W * batch <= 2^26 (K4_ERR_UNSUPPORTED above).  w_split = k4_vgg_pack_weight(..., K4_VGG_CONV_FWD)
  *   K4_VGG_CONV_DGRAD  x = dY with cin = the layer's outputs, y = dX with cout = the layer's inputs: v = sum dY[p + 1 - d][co] W[co][ci][d];
  *                      y = (mask == NULL || mask[.] > 0 ? v : 0) + (add == NULL ? 0 : add[.]): the ReLU backward of the layer that produced this layer's input, from its
  *                      saved activation (torch's rule: act > 0), and a loss seed added on the way.  w_split = k4_vgg_pack_weight(..., K4_VGG_CONV_DGRAD)
@@ -911,6 +912,25 @@ int k4_vgg_l1_bwd(const float* a, const float* b, int64_t n, float scale, const 
 int64_t k4_vgg_gram_workspace_bytes(int32_t n_pix, int32_t channels);
 int k4_vgg_gram(const float* f, int32_t n_pix, int32_t channels, float* workspace, int64_t workspace_bytes, float* gram, void* stream);
 int k4_vgg_gram_bwd_pack(const float* gram, int32_t n_pix, int32_t channels, float scale, const float* grad_loss, void* w_split, void* stream);
+
+/* ---- ABI 23 -- LPIPS-VGG frame scoring (csrc/k4_lpips.hip; lib/utils.py:137-149: lpips.LPIPS(net='vgg', version='0.1'), formulas as the published lpips 0.1
+ * source has them).  The backbone is k4_vgg_conv1_1 / k4_vgg_conv3x3 on the two frames as a batch of two (a VGG16, floor-mode pools); these are the heads.
+ * k4_lpips_head: one tap.  f [2][n_pix][channels] post-ReLU features of the two images, w [channels] the tap's 1x1 weights (no bias).  Per pixel
+ *     n_i = f_i / (sqrtf(sum_c f_i[c]^2) + 1e-10f),   v = sum_c w[c] * (n_0[c] - n_1[c])^2,   taps[slot] (fp64) = (sum over pixels of v) / n_pix.
+ *   Elementwise arithmetic (squares, quotients, the difference, its square, the product with w) in fp32; the channel sum of squares (rounded to fp32 in front
+ *   of sqrtf), the weighted channel sum and the pixel sum are fp64 partials added in one fixed order: a wave per pixel on a fixed butterfly, 64 pixels per
+ *   workgroup (each of its four waves adds its 16 pixels in order, then (w0 + w1) + (w2 + w3)) into `workspace` (k4_lpips_workspace_bytes(n_pix) bytes), and a finishing launch over the workgroups in index order.
+ *   A pixel whose features are all zero gives n = 0 / 1e-10 = 0.  No atomics, no host synchronisation: two calls give the same bits, and so does swapping the images.
+ *   channels in {64, 128, 256, 512} and n_pix <= 2^26, else K4_ERR_UNSUPPORTED (the workspace size is then -1).
+ * k4_lpips_total: out [1 + n_taps] fp32 on the device: out[0] = the sum of taps[0 .. n_taps) added in fp64 in index order and rounded to fp32 once, out[1 + k] =
+ *   taps[k] rounded to fp32.  n_taps <= 16.
+ * k4_lpips_check_frame: 0 for a frame the metric can index; K4_ERR_UNSUPPORTED for H or W below 16 (four floor-mode pools: a pooled level would be empty) or
+ *   2 * H * W > 2^26 (the bound of k4_vgg_conv3x3 on the batch of two).  Nothing is ever wrapped or clamped to fit.
+ * All three launching entry points are recordable on a launch tape. */
+int64_t k4_lpips_workspace_bytes(int64_t n_pix);
+int k4_lpips_head(const float* f, int64_t n_pix, int32_t channels, const float* w, void* workspace, double* taps, int32_t slot, void* stream);
+int k4_lpips_total(const double* taps, int32_t n_taps, float* out, void* stream);
+int k4_lpips_check_frame(int32_t H, int32_t W);
 
 /* ---------------------------------------------------------------------------------------------
  * Frame evaluation (csrc/k4_metric.hip): SSIM and the squared-difference sum of two device-resident frames in one pass.
