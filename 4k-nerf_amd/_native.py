@@ -12,7 +12,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('K4_LIB') or os.path.join(_PKG, 'lib4k_hip.so')      # K4_LIB: a variant build (A/B experiments, tools/)
-K4_ABI_VERSION = 23
+K4_ABI_VERSION = 24
 # True: the data-path collectives (tile all-gather, gradient exchange) are issued even on a process group of ONE rank -- the RCCL smoke test
 # on a single GPU (tests/test_rccl_gpu.py: communicator + the production collective calls on device buffers); never set in production
 FORCE_COLLECTIVES = False
@@ -127,6 +127,8 @@ _SIGS = {
     'k4_sample_pts_on_rays_count': [_P, _P, _P, _P, _F, _F, _F, _I64, _P, _P, _P, _P],
     'k4_sample_pts_on_rays_fill': [_P, _P, _P, _P, _P, _P, _F, _I64, _I64, _P, _P, _P, _P, _P],
     'k4_maskcache_lookup': [_P, _P, _P, _P, _I32, _I32, _I32, _I64, _P, _P],
+    'k4_hit_coarse_geo': [_P, _P, _P, _P, _F, _F, _F, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _P],
+    'k4_patch_hit_counts': [_P, _I32, _I32, _I32, _I32, _P, _P],
     'k4_raw2alpha': [_P, _F, _F, _P, _I64, _P, _P, _P],
     'k4_raw2alpha_backward': [_P, _P, _F, _P, _I64, _P, _P],
     'k4_alpha2weight': [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P],
@@ -305,6 +307,7 @@ _EXTRA_SIGS = {
     'k4_grid_sample_3d_backward_terms': ([_P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P, _P], C.c_int),
     'k4_sorted_segment_add': ([_P, _P, _I64, _I64, _P, _P], C.c_int),
     'k4_march_vq_fwd': ([C.POINTER(VqDesc), _P], C.c_int),
+    'k4_patch_hit_entries': ([_I32, _I32, _I32], C.c_int64),
     'k4_frame_metrics': ([_P, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(C.c_double), _I32, C.c_double, C.c_double, _P, _P, _P, _P], C.c_int),
 }
 

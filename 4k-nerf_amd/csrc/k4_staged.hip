@@ -165,6 +165,72 @@ __global__ void k_maskcache(const uint8_t* __restrict__ world, const float* __re
     out[i] = k4s_maskcache(world, xyz[i * 3 + 0], xyz[i * 3 + 1], xyz[i * 3 + 2], sc, sh, si, sj, sk);
 }
 
+// ---------------------------------------------------------------- DirectVoxGO.hit_coarse_geo (lib/dvgo.py:281-293) in one launch
+// "Does a sample of this ray lie inside the box on an occupied cell of the mask cache?" -- the op sequence k_pts_count, cumsum, k_pts_fill,
+// boolean index, k_maskcache, boolean index, scatter, with no sample list in between: one lane walks one ray (consecutive lanes = consecutive
+// pixels of an image row: similar lengths, neighbouring mask bytes) with k_pts_count's t_min / N_steps and k_pts_fill's point expression, so
+// a sample's bits are the staged path's; the walk ends at the first hit.  Nothing but hit[ray] is written.
+__global__ __launch_bounds__(K4_THREADS) void k_hit_coarse_geo(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ mn,
+                                                               const float* __restrict__ mx, float near, float far, float stepdist, int64_t n,
+                                                               const uint8_t* __restrict__ world, const float* __restrict__ sc, const float* __restrict__ sh,
+                                                               int si, int sj, int sk, uint8_t* __restrict__ hit) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const float bmn[3] = {mn[0], mn[1], mn[2]}, bmx[3] = {mx[0], mx[1], mx[2]};       // uniform: once per ray, not once per sample
+    const float msc[3] = {sc[0], sc[1], sc[2]}, msh[3] = {sh[0], sh[1], sh[2]};
+    float t_min, t_max;
+    aabb_t(o, d, mn, mx, near, far, r, t_min, t_max);
+    const float rn = ray_norm(d, r);
+    const int64_t n_steps = n_steps_of(t_min, t_max, rn, stepdist);
+    float start[3], dir[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        start[c] = fmaf(d[r * 3 + c], t_min, o[r * 3 + c]);
+        dir[c] = d[r * 3 + c] / rn;
+    }
+    uint8_t h = 0;
+    for (int64_t step = 0; step < n_steps; ++step) {
+        const float dist = stepdist * (float)step;
+        float p[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = fmaf(dir[c], dist, start[c]);
+        if (k4s_outbbox(p, bmn, bmx)) continue;
+        if (k4s_maskcache(world, p[0], p[1], p[2], msc, msh, si, sj, sk)) { h = 1; break; }
+    }
+    hit[r] = h;
+}
+
+// Hit rays per entry of dvgo.patch_gen((H, W), ., bs * sz, sz) for every view of hit[n_img][H][W], in that list's order: the full bs x bs tiles
+// column band by column band, the right-edge remainders (one per row band), the bottom-edge remainders (one per column band), the corner.
+// One workgroup per (entry, view); an empty entry (an exactly divisible side) counts 0 and keeps its place.
+__global__ __launch_bounds__(K4_THREADS) void k_patch_hit_counts(const uint8_t* __restrict__ hit, int H, int W, int bs, int P, int32_t* __restrict__ counts) {
+    __shared__ int part[K4_THREADS / 64];
+    const int p = blockIdx.x, img = blockIdx.y;
+    const int nr = H / bs, nc = W / bs;
+    int rb, cb;                                                     // row band / column band; nr / nc = the remainder band
+    if (p < nr * nc) { cb = p / nr; rb = p - cb * nr; }
+    else if (p < nr * nc + nr) { rb = p - nr * nc; cb = nc; }
+    else { rb = nr; cb = p - nr * nc - nr; }
+    const int r0 = rb * bs, r1 = rb < nr ? r0 + bs : H;
+    const int c0 = cb * bs, c1 = cb < nc ? c0 + bs : W;
+    const int w = c1 - c0, cnt = (r1 - r0) * w;
+    const uint8_t* const base = hit + (size_t)img * H * W;
+    int acc = 0;
+    for (int i = threadIdx.x; i < cnt; i += K4_THREADS) {
+        const int row = i / w, col = i - row * w;
+        acc += base[(size_t)(r0 + row) * W + c0 + col] != 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    if (k4_lane() == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int i = 0; i < K4_THREADS / 64; ++i) s += part[i];
+        counts[(size_t)img * P + p] = s;
+    }
+}
+
 // ---------------------------------------------------------------- raw2alpha (+bwd) (.cu:431-458, 507-530)
 __global__ void k_raw2alpha(const float* __restrict__ den, float shift, float interval, const float* __restrict__ ipp,
                             int64_t n, float* __restrict__ ex, float* __restrict__ al) {
@@ -901,6 +967,27 @@ extern "C" int k4_maskcache_lookup(const uint8_t* world, const float* xyz, const
     if (n == 0) return K4_OK;
     REQ(xyz && out);
     hipLaunchKernelGGL(k_maskcache, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, world, xyz, sc, sh, si, sj, sk, n, out);
+    return k4_check_launch();
+}
+extern "C" int k4_hit_coarse_geo(const float* o, const float* d, const float* mn, const float* mx, float near, float far, float stepdist,
+                                 int64_t n, const uint8_t* world, const float* sc, const float* sh, int32_t si, int32_t sj, int32_t sk,
+                                 uint8_t* hit, void* stream) {
+    REQ(mn && mx && world && sc && sh && n >= 0 && stepdist > 0.f && si > 0 && sj > 0 && sk > 0);
+    if (n == 0) return K4_OK;
+    REQ(o && d && hit && n <= (int64_t)K4_THREADS * 0x7fffffff);
+    hipLaunchKernelGGL(k_hit_coarse_geo, dim3(k4_blocks(n)), dim3(K4_THREADS), 0, ST, o, d, mn, mx, near, far, stepdist, n, world, sc, sh, si, sj, sk, hit);
+    return k4_check_launch();
+}
+extern "C" int64_t k4_patch_hit_entries(int32_t H, int32_t W, int32_t bs) {
+    if (H <= 0 || W <= 0 || bs <= 0) return -1;
+    return (int64_t)(H / bs) * (W / bs) + H / bs + W / bs + 1;
+}
+extern "C" int k4_patch_hit_counts(const uint8_t* hit, int32_t n_img, int32_t H, int32_t W, int32_t bs, int32_t* counts, void* stream) {
+    const int64_t P = k4_patch_hit_entries(H, W, bs);
+    REQ(P > 0 && P <= 0x7fffffff && n_img >= 0 && n_img <= 65535 && (int64_t)H * W <= 0x7fffffff);
+    if (n_img == 0) return K4_OK;
+    REQ(hit && counts);
+    hipLaunchKernelGGL(k_patch_hit_counts, dim3((unsigned)P, (unsigned)n_img), dim3(K4_THREADS), 0, ST, hit, H, W, bs, (int)P, counts);
     return k4_check_launch();
 }
 extern "C" int k4_raw2alpha(const float* den, float shift, float interval, const float* ipp, int64_t n,

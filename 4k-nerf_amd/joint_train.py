@@ -143,6 +143,20 @@ class JointCfg(dict):
         cfg.update(over)
         return cls.fern_lg_joint_l1(**cfg)
 
+    @classmethod
+    def chair_1x_joint_l1_gan(cls, **over):
+        """configs/syn/1x_chair_joint_l1+gan.py on top of default.py (NOT syn_default.py: no TV terms, no distortion term, N_rand=8192): the synthetic
+        recipe at sr_ratio 1, patches from the 'patch_inmask' sampler (lib/dvgo.get_training_rays_in_maskcache_sampling_sr).  As with
+        ``fern_lg_joint_l1_gan`` the perceptual / style weights need ``cri_perceptual`` and the adversarial weight needs ``net_d``."""
+        cfg = dict(N_iters=300000, N_rand=8192, N_patch=64, ray_sampler='patch_inmask',
+                   lrate_density=1e-1, lrate_k0=1e-1, lrate_rgbnet=1e-3, lrate_srnet=2e-4, lrate_decay=300,
+                   skip_zero_grad_fields=['density', 'k0'],
+                   weight_main=1.0, weight_entropy_last=0.001, weight_nearclip=0, weight_distortion=0, weight_rgbper=0.01,
+                   weight_pcp=0.5, weight_gan=0.05, weight_style=0.2,
+                   tv_every=1, tv_after=0, tv_before=0, tv_dense_before=0, weight_tv_density=0.0, weight_tv_k0=0.0)
+        cfg.update(over)
+        return cls(cfg)
+
 
 class JointTrainer:
     """Optimizers + one-iteration method of the joint loop.  ``render_kwargs`` as run_sr.py:690-702 builds them

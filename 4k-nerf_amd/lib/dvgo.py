@@ -579,6 +579,19 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
         hit[ray_id[inside][occupied]] = True
         return hit.reshape(shape)
 
+    @torch.no_grad()
+    def k4_hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
+        '''``hit_coarse_geo`` in one launch (k4_hit_coarse_geo): the same bits, no sample list in global memory, a ray stops at its first hit,
+        any number of rays per call.  Rays of any leading shape (contiguous or not) -> bool of that shape.'''
+        shape = rays_o.shape[:-1]
+        ro = rays_o.reshape(-1, 3).float().contiguous()
+        rd = rays_d.reshape(-1, 3).float().contiguous()
+        mc = self.mask_cache
+        # far = 1e9 as in hit_coarse_geo
+        hit = render_utils_cuda.hit_coarse_geo(ro, rd, self.xyz_min, self.xyz_max, near, 1e9, stepsize * self.voxel_size,
+                                               mc.mask, mc.xyz2ijk_scale, mc.xyz2ijk_shift)
+        return hit.reshape(shape)
+
     def sample_ray(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         '''Sample query points on rays (lib/dvgo.py:295-325): points sorted near to far.'''
         far = 1e9  # the given far can be too small while rays stop when hitting scene bbox
@@ -1023,6 +1036,108 @@ def get_training_rays_in_maskcache_sampling(rgb_tr_ori, train_poses, HW, Ks, ndc
     rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr = (torch.cat(c, 0) for c in cols)
     print('get_training_rays_in_maskcache_sampling: ratio', rgb_tr.shape[0] / max(total, 1))
     return rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr, imsz
+
+
+def patch_hit_counts(hit, bs):
+    """Hit rays per entry of ``patch_gen((H, W), ., bs * sz, sz)``, in that list's order, for every view (k4_patch_hit_counts).
+    ``hit``: [n_img, H, W] or [H, W], bool or uint8, on the device -> int32 [n_img, P] or [P], P = (H//bs)*(W//bs) + H//bs + W//bs + 1."""
+    if hit.dtype not in (torch.bool, torch.uint8):
+        raise N.K4Error(f'patch_hit_counts: bool or uint8 hit masks expected, got {hit.dtype}')
+    if hit.dim() not in (2, 3):
+        raise N.K4Error('patch_hit_counts: [n_img, H, W] or [H, W] expected')
+    counts = render_utils_cuda.patch_hit_counts((hit[None] if hit.dim() == 2 else hit).contiguous(), bs)
+    return counts[0] if hit.dim() == 2 else counts
+
+
+def select_inmask_patches(counts, imsz, bs, min_hits=2048):
+    """The host half of the 'patch_inmask' sampler: from the per-view, per-entry hit counts [n_img, P] (a host array) keep entry ``p`` of view
+    ``b`` when ``counts[b, p] > min_hits`` (lib/dvgo.py:736-741), in view order, then in list order.
+    -> (patch_all: list of [rows, cols, 2] int64 index arrays, index_all: int64 array of their views).  A list, not upstream's ``np.stack``:
+    kept entries may differ in shape (a remainder band can qualify)."""
+    counts = np.asarray(counts)
+    arr_all = patch_gen(imsz, None, bs, 1)
+    assert counts.ndim == 2 and counts.shape[1] == len(arr_all), (counts.shape, len(arr_all))
+    patch_all, index_all = [], []
+    for b in range(counts.shape[0]):
+        for p in np.flatnonzero(counts[b] > min_hits):
+            patch_all.append(arr_all[p])
+            index_all.append(b)
+    return patch_all, np.asarray(index_all, dtype=np.int64)
+
+
+def inmask_patch_indices_generator(patch_all, index_all):
+    """Endless (image, patch) choices out of the kept patches of the 'patch_inmask' sampler (the generator nested in lib/dvgo.py:698-719): every
+    kept patch once per epoch in a host-side random order -- one ``np.random.permutation`` at the first ``next()`` and one more whenever the
+    list is used up.  Yields ``image, rows, cols, rows_4x, cols_4x, [pr, pc]``; the "4x" lists are the plain ones (the recipe's sr_ratio is 1)."""
+    slots = list(range(len(patch_all)))
+    order, pos = torch.LongTensor(np.random.permutation(slots)), 0
+    while True:
+        if pos >= len(slots):
+            order, pos = torch.LongTensor(np.random.permutation(slots)), 0
+        k = int(order[pos])
+        pos += 1
+        patch = patch_all[k]
+        pr, pc = patch.shape[0], patch.shape[1]
+        rc = patch.reshape(-1, 2)
+        yield index_all[k], list(rc[:, 0]), list(rc[:, 1]), list(rc[:, 0]), list(rc[:, 1]), [pr, pc]
+
+
+@torch.no_grad()
+def get_training_rays_in_maskcache_sampling_sr(rgb_tr_ori, train_poses, HW, Ks, ndc, inverse_y, flip_x, flip_y, model, render_kwargs, cfgs,
+                                               *, patch_rays=4096, sz_patch=64, min_hits=2048):
+    """The 'patch_inmask' ray sampler (lib/dvgo.py:683-758): per-view [N, H, W, 3] tables plus a generator over the tiles of side
+    ``patch_rays // sz_patch`` (64) in which more than ``min_hits`` (2048) rays meet the coarse geometry.  ``cfgs`` is unused, as upstream.
+    -> (rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr, imsz, patch_generator), imsz = hit rays per view.
+    One hit test over all N*H*W rays (model.k4_hit_coarse_geo), one count launch, ONE device-to-host copy (the [N, P] counts); the selection
+    runs on the host.  Where upstream's ``np.stack`` fails this still works (kept tiles of different shapes) or says why (no tile kept)."""
+    n = len(rgb_tr_ori)
+    assert n == len(train_poses) == len(Ks) == len(HW)
+    assert len(np.unique(np.asarray(HW).reshape(n, -1), axis=0)) == 1, 'get_training_rays_in_maskcache_sampling_sr: views of one size only'
+    H, W = (int(v) for v in HW[0])
+    dev = rgb_tr_ori[0].device
+    rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr = (torch.zeros([n, H, W, 3], device=dev) for _ in range(4))
+    for i, (c2w, img, K) in enumerate(zip(train_poses, rgb_tr_ori, Ks)):
+        assert tuple(img.shape[:2]) == (H, W)
+        rgb_tr[i].copy_(img)
+        rays_o_tr[i], rays_d_tr[i], viewdirs_tr[i] = _rays_of((H, W), K, c2w, ndc, inverse_y, flip_x, flip_y, dev)
+    bs = int(patch_rays) // int(sz_patch)
+    hit = model.k4_hit_coarse_geo(rays_o=rays_o_tr, rays_d=rays_d_tr, **render_kwargs)
+    counts = patch_hit_counts(hit, bs).cpu().numpy()                # the one read-back
+    imsz = [int(v) for v in counts.sum(1)]                          # the entries partition a view: their counts add up to its hit rays
+    patch_all, index_all = select_inmask_patches(counts, (H, W), bs, min_hits)
+    if not patch_all:
+        raise ValueError(f'get_training_rays_in_maskcache_sampling_sr: no {bs}x{bs} tile of the {n} views holds more than {min_hits} rays that '
+                         f'meet the coarse geometry (most in one tile: {int(counts.max()) if counts.size else 0})')
+    print('get_training_rays_in_maskcache_sampling: ratio', sum(imsz) / max(n * H * W, 1))
+    return rgb_tr, rays_o_tr, rays_d_tr, viewdirs_tr, imsz, inmask_patch_indices_generator(patch_all, index_all)
+
+
+def batch_images_generator(N, imsz, BS):
+    """Image after image in order, each in consecutive index ranges of at most BS out of imsz (lib/dvgo.py:771-783, the fallback sampler of
+    run_sr.py:757-758).  Yields ``(range, image, last)``; ``last`` marks the range that ends an image -- as upstream that is the one with
+    ``start + BS >= imsz``, so a range of exactly BS that reaches the end is the last one.  No random numbers."""
+    image, pos = 0, 0
+    while True:
+        last = pos + BS >= imsz
+        yield range(pos, imsz if last else pos + BS), image, last
+        if last:
+            image, pos = (image + 1) % N if N > 0 else 0, 0
+        else:
+            pos += BS
+
+
+def simg_patch_indices_generator(imsz, BS):
+    """The 'patch_simg' ray sampler (lib/dvgo.py:786-819): endless patches of one image, tiles of side BS // 64, every entry of ``patch_gen`` once per
+    epoch in a host-side random order (the EMPTY remainder entries of a divisible side take part in the permutation, as upstream).
+    Yields ``[rows, cols]`` (flattened int64 pixel index arrays)."""
+    patches = patch_gen(imsz, None, BS, 64)
+    order, pos = torch.LongTensor(np.random.permutation(len(patches))), 0
+    while True:
+        if pos >= len(patches):
+            order, pos = torch.LongTensor(np.random.permutation(len(patches))), 0
+        rc = patches[int(order[pos])].reshape(-1, 2)
+        pos += 1
+        yield [rc[:, 0], rc[:, 1]]
 
 
 def batch_indices_generator(N, BS):

@@ -103,6 +103,32 @@ def maskcache_lookup(world, xyz, xyz2ijk_scale, xyz2ijk_shift):
     return out
 
 
+def hit_coarse_geo(rays_o, rays_d, xyz_min, xyz_max, near, far, stepdist, world, xyz2ijk_scale, xyz2ijk_shift):
+    """Not one of the reference's 13: ``sample_pts_on_rays`` + ``maskcache_lookup`` + "any sample of the ray inside the box and occupied?" in one
+    launch (k4_hit_coarse_geo), without the sample list.  rays [n, 3] -> bool [n]."""
+    n = rays_o.shape[0]
+    hit = torch.empty([n], dtype=torch.bool, device=rays_o.device)
+    if n == 0:
+        return hit
+    N.check(N.lib().k4_hit_coarse_geo(N.f32(rays_o), N.f32(rays_d), N.f32(xyz_min), N.f32(xyz_max), _f(near), _f(far), _f(stepdist), n,
+                                      N.ptr(world), N.f32(xyz2ijk_scale), N.f32(xyz2ijk_shift), world.shape[0], world.shape[1], world.shape[2],
+                                      N.ptr(hit), N.stream()), 'hit_coarse_geo')
+    return hit
+
+
+def patch_hit_counts(hit, bs):
+    """hit [n_img, H, W] bool / uint8 -> int32 [n_img, P]: the hit rays of every ``patch_gen`` entry for tiles of side ``bs`` (k4_patch_hit_counts)."""
+    n_img, H, W = (int(v) for v in hit.shape)
+    P = int(N.lib().k4_patch_hit_entries(H, W, int(bs)))
+    if P < 0:
+        raise N.K4Error(f'patch_hit_counts: bad arguments (H, W, bs) = {(H, W, bs)}')
+    counts = torch.empty([n_img, P], dtype=torch.int32, device=hit.device)
+    if n_img == 0:
+        return counts
+    N.check(N.lib().k4_patch_hit_counts(N.ptr(hit), n_img, H, W, int(bs), N.ptr(counts), N.stream()), 'patch_hit_counts')
+    return counts
+
+
 def _raw2alpha(density, shift, interval, ipp):
     exp_d = torch.empty_like(density)
     alpha = torch.empty_like(density)

@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      23      /* 23: LPIPS-VGG frame scoring (csrc/k4_lpips.hip): k4_lpips_head(+_workspace_bytes), k4_lpips_total, k4_lpips_check_frame; k4_vgg_conv3x3 takes any H, W >= 1 and pools in floor mode;  22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      24      /* 24: the 'patch_inmask' ray sampler's hit test (csrc/k4_staged.hip): k4_hit_coarse_geo, k4_patch_hit_counts, k4_patch_hit_entries;  23: LPIPS-VGG frame scoring (csrc/k4_lpips.hip): k4_lpips_head(+_workspace_bytes), k4_lpips_total, k4_lpips_check_frame; k4_vgg_conv3x3 takes any H, W >= 1 and pools in floor mode;  22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -249,6 +249,19 @@ int k4_sample_pts_on_rays_fill(const float* rays_o, const float* rays_d, const f
 /* maskcache_lookup (render_utils.cpp:109-118) */
 int k4_maskcache_lookup(const uint8_t* world, const float* xyz, const float* xyz2ijk_scale, const float* xyz2ijk_shift,
                         int32_t sz_i, int32_t sz_j, int32_t sz_k, int64_t n_pts, uint8_t* out, void* stream);
+/* DirectVoxGO.hit_coarse_geo (lib/dvgo.py:281-293) in one launch: hit[r] = 1 when a sample of ray r -- the samples of sample_pts_on_rays(near, far,
+ * stepdist), bit for bit -- lies inside [xyz_min, xyz_max] and the nearest-voxel lookup of `world` [sz_i][sz_j][sz_k] there is non-zero.  A ray's walk
+ * ends at its first hit; no per-sample value is written.  xyz_min / xyz_max / xyz2ijk_* are DEVICE pointers as in the staged ops.  Any n_rays;
+ * n_rays == 0 returns without a launch. */
+int k4_hit_coarse_geo(const float* rays_o, const float* rays_d, const float* xyz_min, const float* xyz_max, float near, float far, float stepdist,
+                      int64_t n_rays, const uint8_t* world, const float* xyz2ijk_scale, const float* xyz2ijk_shift,
+                      int32_t sz_i, int32_t sz_j, int32_t sz_k, uint8_t* out_hit, void* stream);
+/* Hit rays per patch of the 'patch_inmask' ray sampler: hit = [n_img][H][W] bytes; counts = [n_img][P] int32, one per entry of the reference's
+ * patch_gen (lib/dvgo.py:822-848) for tiles of side bs, in its order: (H / bs) * (W / bs) full tiles column band by column band, H / bs right-edge
+ * remainders, W / bs bottom-edge remainders, the corner.  Empty entries (an exactly divisible side) count 0.  k4_patch_hit_entries -> P (host
+ * only; < 0: bad arguments). */
+int64_t k4_patch_hit_entries(int32_t H, int32_t W, int32_t bs);
+int k4_patch_hit_counts(const uint8_t* hit, int32_t n_img, int32_t H, int32_t W, int32_t bs, int32_t* out_counts, void* stream);
 /* raw2alpha / raw2alpha_backward (render_utils.cpp:120-135); interval_pp != NULL -> the _nonuni variants (:125-140) */
 int k4_raw2alpha(const float* density, float shift, float interval, const float* interval_pp, int64_t n_pts,
                  float* out_exp, float* out_alpha, void* stream);
