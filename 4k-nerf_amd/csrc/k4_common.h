@@ -31,6 +31,44 @@ __device__ __forceinline__ int k4_run_id(int key, int lane) {
     return __popcll(heads & (~0ull >> (63 - lane)));
 }
 
+// ---- cheaper instruction forms for the marcher's FAST geometry instantiation (profiles/march_index32.md) --------------
+// Load / store at a wave-UNIFORM base + an unsigned 32-bit per-lane byte offset: the SGPR-base form of global_load / global_store (the offset is
+// zero-extended by the instruction), no 64-bit per-lane address arithmetic.  base + off must lie inside the array: nothing clamps.
+template <class T> __device__ __forceinline__ T k4_ld_off(const void* base, unsigned off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+}
+template <class T> __device__ __forceinline__ void k4_st_off(void* base, unsigned off, const T& v) {
+    *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off) = v;
+}
+
+// Inclusive integer add-scan over the 64 lanes of a wave without LDS traffic: four row_shr steps inside each row of 16 lanes (lanes a shift
+// would read from outside the row add 0), then the last lane of row 0 / 2 to every lane of row 1 / 3 (row_bcast:15, row mask 0xa) and lane 31
+// to rows 2 and 3 (row_bcast:31, row mask 0xc).  Six v_add_u32_dpp against the six ds_bpermute_b32 round trips of the __shfl_up form; the
+// same integer adds in another association, so the same sums.  Every lane of the wave must be active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int k4_dpp_or0(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
+__device__ __forceinline__ int k4_wave_scan_add(int v) {
+    v += k4_dpp_or0<0x111, 0xf>(v);       // row_shr:1
+    v += k4_dpp_or0<0x112, 0xf>(v);       // row_shr:2
+    v += k4_dpp_or0<0x114, 0xf>(v);       // row_shr:4
+    v += k4_dpp_or0<0x118, 0xf>(v);       // row_shr:8
+    v += k4_dpp_or0<0x142, 0xa>(v);       // row_bcast:15
+    v += k4_dpp_or0<0x143, 0xc>(v);       // row_bcast:31
+    return v;
+}
+// max over the 64 lanes of a wave by the same six steps (a lane without a source keeps its own value), returned wave-uniform from lane 63
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int k4_dpp_self(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false); }
+__device__ __forceinline__ int k4_wave_max(int v) {
+    v = max(v, k4_dpp_self<0x111, 0xf>(v));
+    v = max(v, k4_dpp_self<0x112, 0xf>(v));
+    v = max(v, k4_dpp_self<0x114, 0xf>(v));
+    v = max(v, k4_dpp_self<0x118, 0xf>(v));
+    v = max(v, k4_dpp_self<0x142, 0xa>(v));
+    v = max(v, k4_dpp_self<0x143, 0xc>(v));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
 // LDS accumulate (ds_add_f32 / ds_add_f64 / ds_add_u64, no return value)
 __device__ __forceinline__ void k4_lds_add(unsigned long long* p, unsigned long long v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -50,6 +88,11 @@ __device__ __forceinline__ float k4_readlane(float v, int l) {
 struct __attribute__((packed, aligned(4))) k4_f2u { float x, y; };
 __device__ __forceinline__ float2 k4_ld2(const float* p) {
     const k4_f2u v = *reinterpret_cast<const k4_f2u*>(p);
+    return make_float2(v.x, v.y);
+}
+
+__device__ __forceinline__ float2 k4_ld2_off(const float* base, unsigned off) {     // the same fetch at base + a 32-bit byte offset (k4_ld_off below)
+    const k4_f2u v = *reinterpret_cast<const k4_f2u*>(reinterpret_cast<const char*>(base) + off);
     return make_float2(v.x, v.y);
 }
 

@@ -37,6 +37,7 @@
 // Deterministic: no global atomics on the data path, fixed summation order.
 #include "k4_common.h"
 #include "k4_geom_deal.h"
+#include "k4_index32.h"
 #include <string.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -185,6 +186,20 @@ __device__ __forceinline__ void ray_setup(const MarchParams& P, float ox, float 
 #ifndef K4_GEOM_LDS_PAD
 #define K4_GEOM_LDS_PAD 0            // A/B builds only: see the kernel
 #endif
+// Cheaper instructions in the FAST geometry instantiation (profiles/march_index32.md).  Compile-time A/B switches (tools/build_variant.sh <tag>
+// -DK4_IDX_...=0), never read at run time; each leaves every index, every loaded value and every stored record what the general form gives:
+//   K4_IDX_OFF32   every global access of the probe, stages A and B and the tail as a uniform base + an unsigned 32-bit per-lane BYTE offset
+//                  (k4_ld_off / k4_st_off: the SGPR-base form of global_load / global_store) instead of 64-bit per-lane address arithmetic;
+//                  rests on the host predicate k4_march_index32_ok;
+//   K4_IDX_DPP     the tail's prefix scans and the prologue's group-count maximum through DPP (k4_wave_scan_add, k4_wave_max).
+// (Not in the tree, profiles/march_index32.md: 24-bit multiply-adds for the indices -- v_mad_u32_u24 issues no faster than v_mul_lo_u32 on
+// gfx950 -- and a per-group box certificate from the probe that let stage A skip the per-sample box test, which measured 5 us slower.)
+#ifndef K4_IDX_OFF32
+#define K4_IDX_OFF32 1
+#endif
+#ifndef K4_IDX_DPP
+#define K4_IDX_DPP 1
+#endif
 #define K4_RING 512
 #define K4_TKTAB 256              // MPI: k/(Ns-1) for k < K4_TKTAB is tabulated once per workgroup (an IEEE division costs ~10 VALU per sample)
 #define K4_ELIST 512              // kept (ray, group) entries enumerated at a time (ray sub-batches when 64 rays x groups exceed it)
@@ -317,9 +332,12 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
     if (abl & 4096) ngrp = 0;                                           // ablation (WRONG results): prologue, arrival and the empty scan only -- the kernel's fixed cost
     if (abl & 8192) { if (lane == 0 && wv == 0) P.counts[B.id] = 0; break; } // ablation: not even the arrival / scan
     int gq = ngrp;
+    if constexpr (FAST && K4_IDX_DPP) gq = k4_wave_max(ngrp);           // (every lane is here: the exits above are wave-uniform)
+    else {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) gq = max(gq, __shfl_xor(gq, off));
-    gq = __builtin_amdgcn_readfirstlane(gq);
+        for (int off = 32; off > 0; off >>= 1) gq = max(gq, __shfl_xor(gq, off));
+        gq = __builtin_amdgcn_readfirstlane(gq);
+    }
     // FAST: MPI rays take nsteps == n_samples <= K4_TKTAB samples (host predicate), so a depth quarter is one 64-sample block: at most 4 groups,
     // and every k formed below is < roundup16(n_samples) <= K4_TKTAB -- the table reads tktab[k] rest on both
     static_assert(K4_TKTAB <= 256 && K4_TKTAB % K4_GRP == 0, "FAST: one 64-sample block per depth quarter, k < K4_TKTAB");
@@ -354,6 +372,11 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
             unsigned long long win = 0ull;
             if (!empty) {
                 const unsigned tab = (unsigned)((sx > 0) + 2 * (sy > 0));
+                if constexpr (FAST && K4_IDX_OFF32) {
+                    // the same window by a 32-bit index: the four tables hold < 2^29 windows (idx32), so nothing wraps
+                    const unsigned wi = tab * (unsigned)ntab + (unsigned)(cx0 * ncy + cy0) * (unsigned)zw + (unsigned)(z0 >> 5);
+                    win = k4_ld_off<unsigned long long>(P.occ, wi << 3);
+                } else
                 win = P.occ[(size_t)tab * (size_t)ntab + (size_t)(cx0 * ncy + cy0) * (size_t)zw + (size_t)(z0 >> 5)];
             }
             const int len = z1 - z0 + 1;
@@ -406,8 +429,15 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
 #pragma unroll
                 for (int c4 = 0; c4 < 4; ++c4) pdl[s2][c4] = pdh[s2][c4] = c;
             } else if (FAST || P.Z >= 2) {
-                const float2 v0 = k4_ld2(P.density + r00 + zb), v1 = k4_ld2(P.density + r01 + zb);
-                const float2 v2 = k4_ld2(P.density + r10 + zb), v3 = k4_ld2(P.density + r11 + zb);
+                float2 v0, v1, v2, v3;
+                if constexpr (FAST && K4_IDX_OFF32) {                     // byte offsets < 4 X Y Z < 2^32 (idx32)
+                    const unsigned zb4 = (unsigned)zb << 2;
+                    v0 = k4_ld2_off(P.density, (r00 << 2) + zb4); v1 = k4_ld2_off(P.density, (r01 << 2) + zb4);
+                    v2 = k4_ld2_off(P.density, (r10 << 2) + zb4); v3 = k4_ld2_off(P.density, (r11 << 2) + zb4);
+                } else {
+                    v0 = k4_ld2(P.density + r00 + zb); v1 = k4_ld2(P.density + r01 + zb);
+                    v2 = k4_ld2(P.density + r10 + zb); v3 = k4_ld2(P.density + r11 + zb);
+                }
                 pdl[s2][0] = v0.x; pdh[s2][0] = v0.y; pdl[s2][1] = v1.x; pdh[s2][1] = v1.y;
                 pdl[s2][2] = v2.x; pdh[s2][2] = v2.y; pdl[s2][3] = v3.x; pdh[s2][3] = v3.y;
             } else {                                                      // single-plane grid: both z corners are plane 0
@@ -419,7 +449,11 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
                 const float ua = k4_unnorm(nz, P.act_d);
                 const int a0 = (int)floorf(ua);
                 pfa[s2] = ua;
-                pa0[s2] = P.act_shift[a0]; pa1[s2] = P.act_shift[min(a0 + 1, P.act_d - 1)];
+                if constexpr (FAST && K4_IDX_OFF32) {                     // act_d < 2^24 (launch_march)
+                    pa0[s2] = k4_ld_off<float>(P.act_shift, (unsigned)a0 << 2); pa1[s2] = k4_ld_off<float>(P.act_shift, (unsigned)min(a0 + 1, P.act_d - 1) << 2);
+                } else {
+                    pa0[s2] = P.act_shift[a0]; pa1[s2] = P.act_shift[min(a0 + 1, P.act_d - 1)];
+                }
             }
         }
         pend_n = nproc;
@@ -464,7 +498,8 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
                 K4_DEAL_PUT(0, nq0); K4_DEAL_PUT(1, nq1); K4_DEAL_PUT(2, nq2); K4_DEAL_PUT(3, nq3);
 #undef K4_DEAL_PUT
                 if (act) {
-                    ent_base[dst] = make_uint2(key, __float_as_uint(alpha));
+                    if constexpr (K4_IDX_OFF32) k4_st_off<uint2>(ent_base, (unsigned)dst << 3, make_uint2(key, __float_as_uint(alpha)));     // dst < ent_stride: < 2^32 bytes (idx32)
+                    else ent_base[dst] = make_uint2(key, __float_as_uint(alpha));
                     atomicAdd(&L.acnt[(int)(key >> 24)], 1 << (8 * qd));
                 }
             } else {
@@ -550,6 +585,8 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
                 const int mk = k4_round_half_away(fmaf(pz, P.msz, P.mtz));
                 const bool ok = inb && (unsigned)mi < (unsigned)P.MX && (unsigned)mj < (unsigned)P.MY && (unsigned)mk < (unsigned)P.MZ;
                 const unsigned midx = ok ? (unsigned)(mi * P.MY + mj) * (unsigned)P.MZ + (unsigned)mk : 0u;    // < 2^32 mask voxels
+                if constexpr (FAST && K4_IDX_OFF32) mbyte[j] = ok ? (unsigned)k4_ld_off<uint8_t>(P.mask, midx) : 0u;
+                else
                 mbyte[j] = ok ? (unsigned)P.mask[midx] : 0u;
                 inbv[j] = inb;
                 ikey[j] = ((unsigned)r_ << 24) | (unsigned)k;
@@ -608,6 +645,9 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
         // So the two regions never meet and the pointers below do not alias.
         uint2* __restrict__ const surv = ent_base;
         const uint2* __restrict__ const raw = ent_base;
+        // record i of the slice: 8 i < 2^32 bytes (idx32), so the uniform slice base + a 32-bit byte offset reaches it
+        auto rec_ld = [&](int i) -> uint2 { if constexpr (K4_IDX_OFF32) return k4_ld_off<uint2>(raw, (unsigned)i << 3); else return raw[i]; };
+        auto rec_st = [&](int i, const uint2& v) { if constexpr (K4_IDX_OFF32) k4_st_off<uint2>(surv, (unsigned)i << 3, v); else surv[i] = v; };
         const bool any_rec = (na_sh[0] | na_sh[1] | na_sh[2] | na_sh[3]) != 0;              // (wave-uniform) a bundle without records: nothing to scan
         const int skew = k4_deal_skew(lane);
 #pragma unroll
@@ -620,11 +660,16 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
             const int cv2 = (lds_all[2].acnt[lane] >> (8 * w)) & 0xff, cv3 = (lds_all[3].acnt[lane] >> (8 * w)) & 0xff;
             const int p01 = cv0 | (cv1 << 16), p23 = cv2 | (cv3 << 16);
             int i01 = p01, i23 = p23;
+#if K4_IDX_DPP
+            // (all 64 lanes are here: the quarter loop's exits are wave-uniform.  Integer adds of the same 16-bit pairs: the same piece starts)
+            i01 = k4_wave_scan_add(p01); i23 = k4_wave_scan_add(p23);
+#else
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
                 const int v01 = __shfl_up(i01, off), v23 = __shfl_up(i23, off);
                 if (lane >= off) { i01 += v01; i23 += v23; }
             }
+#endif
             i01 -= p01; i23 -= p23;
             const int u0 = cv0 | ((i01 & 0xffff) << 8), u1 = cv1 | ((i01 >> 16) << 8), u2 = cv2 | ((i23 & 0xffff) << 8), u3 = cv3 | ((i23 >> 16) << 8);
             const bool s1 = (skew & 1) != 0, s2 = (skew & 2) != 0;
@@ -646,7 +691,7 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
             // younger than the records it needs is in flight -- the next step's loads and this step's stores fly under the arithmetic.
             uint2 en[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) en[u] = (u < c && !stopped) ? raw[rec_at(u)] : make_uint2(0u, 0u);
+            for (int u = 0; u < 4; ++u) en[u] = (u < c && !stopped) ? rec_ld(rec_at(u)) : make_uint2(0u, 0u);
             uint2 pe[4];                                               // survivors of the previous step: {key, weight} ...
             int ppos[4];                                               // ... and where they go
             bool pshade[4] = {false, false, false, false};
@@ -657,10 +702,10 @@ __global__ __launch_bounds__(256, FAST ? 7 : MINW) void k4_geom3_kernel(const Ma
                 for (int u = 0; u < 4; ++u) { e[u] = en[u]; asm volatile("" : "+v"(e[u].x), "+v"(e[u].y)); }      // the step's one vmcnt wait lands here
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) if (pshade[u]) surv[ppos[u]] = pe[u];
+                for (int u = 0; u < 4; ++u) if (pshade[u]) rec_st(ppos[u], pe[u]);
                 if (!more) break;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) en[u] = (j0 + 4 + u < c && !stopped) ? raw[rec_at(j0 + 4 + u)] : make_uint2(0u, 0u);
+                for (int u = 0; u < 4; ++u) en[u] = (j0 + 4 + u < c && !stopped) ? rec_ld(rec_at(j0 + 4 + u)) : make_uint2(0u, 0u);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -1220,6 +1265,9 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
     if (nwg <= 0) return K4_OK;
     const dim3 grid(nwg), block(256);
     const int n_cu = k4_num_cus();
+    const bool mask24 = P.MX < (1 << 24) && P.MY < (1 << 24) && P.MZ < (1 << 24);             // (else the predicate fails on the dimension itself)
+    const int64_t occ_windows = !mask24 ? 0 : (int64_t)((P.MX + K4_OCC_CELL - 1) >> K4_OCC_SHIFT) * ((P.MY + K4_OCC_CELL - 1) >> K4_OCC_SHIFT) * ((P.MZ + 31) >> 5);
+    const bool idx32 = k4_index32_ok(P.X, P.Y, P.Z, P.MX, P.MY, P.MZ, occ_windows * 4 * 8, (int64_t)P.ent_stride * (int64_t)sizeof(uint2)) != 0;
     {
         // one workgroup (4 waves = 4 depth quarters) per bundle
         // MINW = waves per SIMD the register allocation is bounded for: 5 (general path: 96 VGPRs, 4 spilled; 6 = 80 VGPRs spills 17 registers, measured
@@ -1227,12 +1275,16 @@ static int launch_march(const MarchParams& P, const k4_mlp_desc* mlp, hipStream_
         // under the bound of 5): its residency is set by the 22 KB of LDS -- 7 workgroups per CU (profiles/geom_tail_append.md, geom_wave_deal.md)
         // FAST: the LLFF configuration (see k4_geom3_kernel); anything else -- DVGO, the counting instantiation, a split scene, stepsize != 1,
         // a scene without the occupancy summary, more than K4_TKTAB samples, any ablation bit the kernel reads -- takes the general instantiation
+        // ... and a grid beyond the 24-bit / 32-bit limits of the FAST index arithmetic (idx32: k4_index32.h -- X*Y, MX*MY, Z, MZ below 2^24;
+        // density bytes, mask voxels, the summary's tables and a bundle's workspace slice below 2^32.  The LLFF grid, 417 x 353 x 256, is far inside)
         const bool gfast = MODE == MODE_MPI && !P.counters && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr &&
-                           P.Z >= 2 && P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom;
+                           P.Z >= 2 && P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom && idx32 &&
+                           P.act_d < (1 << 24);                           // (act_shift byte offsets in 32 bits too)
 #ifdef K4_GEOM_TIMING
         if (P.counters) { MarchParams Q = P; Q.timing = P.counters + 8; Q.counters = nullptr;       // the instantiation the render path would take
                           const bool tfast = MODE == MODE_MPI && P.split_k == 0 && P.interval == 1.f && P.thres > 0.f && P.occ != nullptr && P.Z >= 2 &&
-                                             P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom;
+                                             P.n_samples <= K4_TKTAB && !K4_ABL(P.ablate, K4_GEOM_ABLATE_BITS) && !k4_env().no_fast_geom && idx32 &&
+                                             P.act_d < (1 << 24);
                           if (tfast) hipLaunchKernelGGL((k4_geom3_kernel<MODE_MPI, false, 5, true>), dim3((unsigned)nwg * 4), block, 0, st, Q);
                           else hipLaunchKernelGGL((k4_geom3_kernel<MODE, false, 5>), dim3((unsigned)nwg * 4), block, 0, st, Q); } else
 #endif
@@ -1382,6 +1434,11 @@ static void set_depth_fx(MarchParams& P, int max_steps) {
 }
 
 extern "C" int k4_abi_version(void) { return K4_ABI_VERSION; }
+
+// the index-range part of the geometry kernel's FAST predicate (k4_index32.h), exported so that a host test can call it; launch_march calls the same function
+extern "C" int k4_march_index32_ok(int64_t x, int64_t y, int64_t z, int64_t mx, int64_t my, int64_t mz, int64_t occ_bytes, int64_t slice_bytes) {
+    return k4_index32_ok(x, y, z, mx, my, mz, occ_bytes, slice_bytes);
+}
 
 int k4_num_cus() {
     static int n_cu[K4_MAX_DEVICES];

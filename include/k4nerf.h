@@ -172,6 +172,10 @@ int k4_mlp_b2_layer1_terms(void);    /* NT1 of the default section: 2 (3 in A/B 
  * while it loads (csrc/k4_env.h).
  * ------------------------------------------------------------------------------------------- */
 int64_t k4_march_workspace_bytes(int64_t n_rays, int32_t img_w, int32_t max_steps);
+/* The index-range part of the geometry kernel's FAST predicate (csrc/k4_index32.h), as a pure host function for tests: 1 when X*Y, MX*MY, Z, MZ
+ * are below 2^24 and the density bytes (4 X Y Z), the mask voxels, occ_bytes (the summary's four tables) and slice_bytes (a bundle's workspace
+ * slice) are below 2^32; a grid beyond any of them takes the general instantiation.  No device call, no state. */
+int k4_march_index32_ok(int64_t x, int64_t y, int64_t z, int64_t mx, int64_t my, int64_t mz, int64_t occ_bytes, int64_t slice_bytes);
 
 int k4_march_mpi_fwd(const float* rays_o, const float* rays_d, const float* viewdirs,
                      int64_t n_rays, int32_t img_w,
