@@ -31,6 +31,20 @@ DEPTH_SPLIT_MIN_OPAQUE = 0.5    # ... and smallest share of occupied z columns a
 from .dvgo import Raw2Alpha, Alphas2Weights, render_utils_cuda, _FusedMarcher, segment_sum, coarse_mask_on_grid, _take
 
 
+def depth_split_of(stats, n_samples, min_gain, min_opaque):
+    """k4_grid_desc.depth_split from the statistic of k4_mpi_depth_split_stats (``stats[0:8]``, include/k4nerf.h): among the multiples k of 64 below
+    ``n_samples`` the one whose depth eighth b = min(7, 8 k // n_samples) holds the largest share stats[b] of skippable voxels (b == 0 never counts;
+    of equal shares the smallest k), if that share is at least ``min_gain`` and stats[0], the share of occupied columns that stop a ray, at least
+    ``min_opaque``; else 0, the single launch."""
+    best, gain = 0, 0.0
+    for k in range(64, int(n_samples), 64):
+        b = min(7, (k * 8) // int(n_samples))
+        if b >= 1 and stats[b] > gain:
+            best, gain = k, stats[b]
+    use = gain >= min_gain and stats[0] >= min_opaque
+    return int(best if use else 0)
+
+
 '''Model'''
 def _mlp(dim_in, width, depth, dim_out):
     """Linear-ReLU stack with the reference's module nesting (state-dict keys '0', '2.0', ..., lib/dmpigo.py:112-120); the last
@@ -296,13 +310,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
             N.check(N.lib().k4_mpi_depth_split_stats(N.C.byref(gd), float(interval), float(self.fast_color_thres), N.f32(out), N.stream()),
                     'k4_mpi_depth_split_stats')
             st = out.cpu().tolist()
-            best, gain = 0, 0.0
-            for k in range(64, int(n_samples), 64):
-                b = min(7, (k * 8) // int(n_samples))
-                if b >= 1 and st[b] > gain:
-                    best, gain = k, st[b]
-            use = gain >= DEPTH_SPLIT_MIN_GAIN and st[0] >= DEPTH_SPLIT_MIN_OPAQUE
-            c['dsplit_key'], c['dsplit'], c['dsplit_stats'] = key, (best if use else 0), st[:8]
+            c['dsplit_key'], c['dsplit'], c['dsplit_stats'] = key, depth_split_of(st, n_samples, DEPTH_SPLIT_MIN_GAIN, DEPTH_SPLIT_MIN_OPAQUE), st[:8]
         return int(c['dsplit'])
 
     def _select_samples(self, rays_o, rays_d, N_samples, interval):
