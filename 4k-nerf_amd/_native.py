@@ -189,6 +189,9 @@ _EXTRA_SIGS = {
     'k4_adam_upd': ([_P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F, _P], C.c_int),
     'k4_masked_adam_upd': ([_P, _P, _P, _P, _I64, _I32, _F, _F, _F, _F, _P], C.c_int),
     'k4_masked_adam_upd_sparse_cl': ([_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P], C.c_int),
+    'k4_scatter_image_list': ([_P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P], C.c_int),
+    'k4_scatter_image_take': ([_P, _I32, _I32, _I32, _I32, _P, _I64, _I64, _P, _P], C.c_int),
+    'k4_scatter_image_add': ([_P, _I32, _I32, _I32, _I32, _P, _P, _I64, _I64, _F, _P], C.c_int),
     'k4_grid_flag_corners': ([_I32, _I32, _I32, _P, _P, _P, _I64, _P, _P], C.c_int),
     'k4_masked_adam_upd_unflagged': ([_P, _P, _P, _P, _I32, _I64, _P, _I32, _F, _F, _F, _F, _I32, _P], C.c_int),
     'k4_masked_adam_upd_sparse_cl_seeded': ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P], C.c_int),

@@ -11,6 +11,7 @@
 #include "k4_common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <mutex>
 
 #define K4_OPT_THREADS 256
 
@@ -205,6 +206,171 @@ extern "C" int k4_masked_adam_upd_sparse_cl_seeded(float* param, float* exp_avg,
     const float step_size = lr * sqrtf(1.f - powf(beta2, (float)step)) / (1.f - powf(beta1, (float)step));      // adam_upd_kernel.cu:71
     hipLaunchKernelGGL(k4_adam_sparse_cl_seeded_kernel, dim3((unsigned)blocks), dim3(K4_OPT_THREADS), 0, (hipStream_t)stream, (float*)workspace,
                        (uint8_t*)workspace + nvox * C * 4, flags, seed, C, nvox, param, exp_avg, exp_avg_sq, step_size, beta1, beta2, eps);
+    return k4_check_launch();
+}
+// ------------------------------------------------------------------------------------------------ the scratch image as the data-parallel message
+// Under data parallelism the iterations without TV keep k0's gradient in the scatter's image too (joint_train.exchange_gradients -> lib/grid.GridGrad.exchange):
+// every rank LISTS its flagged voxels, TAKES their sums out of the image into the exchange's message ([cap] int32 indices | [C][cap] fp32 values, the format of
+// sparse_grad_allreduce), and after one all-gather ADDS every rank's list back in rank order -- the image then holds the averaged sums of the union of the ranks'
+// voxels, bit-identical on every replica, and k4_masked_adam_upd_sparse_cl above steps from it as in a single-process job.  What the dense form of the exchange
+// costs per iteration on the LLFF k0 -- 1.36 GB cleared, swept into, scanned (4 C bytes per voxel) for the touched voxels and read again by the optimizer -- is one
+// pass over the 37.7 MB of flag bytes here.
+//   list: ascending order without a sort or an atomic.  Pass 1: a workgroup counts the non-zero flags of K4_IMG_LIST_SPAN consecutive bytes (one 16-byte load per
+//         lane, a wave ballot + popcount per byte position); one workgroup turns the counts into exclusive prefixes (every thread a contiguous slice); pass 2
+//         reads the flags again and writes voxel indices from its workgroup's prefix on (lane prefix: DPP add-scan of the per-lane popcounts).
+//         The flag array starts nvox*C*4 bytes into a 16-byte aligned workspace -- 4-byte aligned only: the 16-byte chunks are laid on ALIGNED addresses, and the
+//         first and last chunk (voxels below 0 / from nvox on masked out) are read byte by byte.
+#define K4_IMG_LIST_THREADS 256
+#define K4_IMG_LIST_SPAN (K4_IMG_LIST_THREADS * 16)            // flag bytes per workgroup
+// bit j of the result: flag byte j of aligned chunk `q` is non-zero and belongs to a voxel in [0, nvox); *v0 = the voxel of byte 0 (may be negative in chunk 0)
+__device__ __forceinline__ unsigned k4_img_chunk_mask(const uint8_t* __restrict__ aligned, int shift, int64_t nvox, int64_t q, int64_t* v0) {
+    const int64_t first = q * 16 - shift;
+    *v0 = first;
+    if (first >= nvox || first + 16 <= 0) return 0u;
+    unsigned m = 0u;
+    if (first >= 0 && first + 16 <= nvox) {
+        const uint4 w = *reinterpret_cast<const uint4*>(aligned + q * 16);
+        const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m |= ((d[j >> 2] >> (8 * (j & 3))) & 0xffu) ? (1u << j) : 0u;
+    } else {
+        for (int j = 0; j < 16; ++j) {
+            const int64_t v = first + j;
+            if (v >= 0 && v < nvox && aligned[q * 16 + j] != 0) m |= 1u << j;
+        }
+    }
+    return m;
+}
+__global__ __launch_bounds__(K4_IMG_LIST_THREADS) void k4_img_list_count_kernel(const uint8_t* __restrict__ aligned, int shift, int64_t nvox, uint32_t* __restrict__ counts) {
+    __shared__ int wave_n[K4_IMG_LIST_THREADS / K4_WAVE];
+    int64_t v0;
+    const unsigned m = k4_img_chunk_mask(aligned, shift, nvox, (int64_t)blockIdx.x * K4_IMG_LIST_THREADS + threadIdx.x, &v0);
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) n += __popcll(__ballot((m >> j) & 1u));       // wave-uniform
+    if (k4_lane() == 0) wave_n[threadIdx.x / K4_WAVE] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < K4_IMG_LIST_THREADS / K4_WAVE; ++w) s += wave_n[w];
+        counts[blockIdx.x] = (uint32_t)s;
+    }
+}
+// counts[nb] -> exclusive prefixes in place, *total = their sum.  One workgroup: thread t owns the slice [t * per, (t + 1) * per)
+__global__ __launch_bounds__(K4_IMG_LIST_THREADS) void k4_img_list_scan_kernel(uint32_t* __restrict__ counts, int64_t nb, int64_t per, int64_t* __restrict__ total) {
+    __shared__ int wave_sum[K4_IMG_LIST_THREADS / K4_WAVE];
+    const int64_t lo = (int64_t)threadIdx.x * per, hi = lo + per < nb ? lo + per : nb;
+    int s = 0;
+    for (int64_t i = lo; i < hi; ++i) s += (int)counts[i];
+    const int incl = k4_wave_scan_add(s);
+    if (k4_lane() == K4_WAVE - 1) wave_sum[threadIdx.x / K4_WAVE] = incl;
+    __syncthreads();
+    int base = incl - s;
+    for (int w = 0; w < (int)(threadIdx.x / K4_WAVE); ++w) base += wave_sum[w];
+    if (threadIdx.x == K4_IMG_LIST_THREADS - 1) *total = (int64_t)(base + s);
+    for (int64_t i = lo; i < hi; ++i) {
+        const int c = (int)counts[i];
+        counts[i] = (uint32_t)base;
+        base += c;
+    }
+}
+__global__ __launch_bounds__(K4_IMG_LIST_THREADS) void k4_img_list_write_kernel(const uint8_t* __restrict__ aligned, int shift, int64_t nvox,
+                                                                                 const uint32_t* __restrict__ prefix, int32_t* __restrict__ out, int64_t cap) {
+    __shared__ int wave_sum[K4_IMG_LIST_THREADS / K4_WAVE];
+    int64_t v0;
+    const unsigned m = k4_img_chunk_mask(aligned, shift, nvox, (int64_t)blockIdx.x * K4_IMG_LIST_THREADS + threadIdx.x, &v0);
+    const int mine = __popc(m);
+    const int incl = k4_wave_scan_add(mine);
+    if (k4_lane() == K4_WAVE - 1) wave_sum[threadIdx.x / K4_WAVE] = incl;
+    __syncthreads();
+    int64_t pos = (int64_t)prefix[blockIdx.x] + (incl - mine);
+    for (int w = 0; w < (int)(threadIdx.x / K4_WAVE); ++w) pos += wave_sum[w];
+    for (unsigned r = m; r != 0u; r &= r - 1u, ++pos)
+        if (pos < cap) out[pos] = (int32_t)(v0 + (__ffs((int)r) - 1));
+}
+// the per-workgroup counts: one buffer per device, kept; a call waits (on its stream) for the previous call's last read of it
+static struct { uint32_t* buf; int64_t n; hipEvent_t ev; } k4_img_list_tmp[K4_MAX_DEVICES];
+static std::mutex k4_img_list_lock;
+extern "C" int k4_scatter_image_list(const void* workspace, int32_t C, int32_t X, int32_t Y, int32_t Z, int32_t* idx_out, int64_t cap, int64_t* counter, void* stream) {
+    if (!workspace || (((uintptr_t)workspace) & 15) || C <= 1 || C > 32 || X <= 0 || Y <= 0 || Z <= 0 || cap < 0 || (cap > 0 && !idx_out) || !counter) return K4_ERR_BAD_ARG;
+    const int64_t nvox = (int64_t)X * Y * Z;
+    if (nvox >= (1ll << 31)) return K4_ERR_BAD_ARG;
+    const uint8_t* const flags = (const uint8_t*)workspace + nvox * C * 4;
+    const int shift = (int)((uintptr_t)flags & 15u);
+    const int64_t nb = (nvox + shift + K4_IMG_LIST_SPAN - 1) / K4_IMG_LIST_SPAN;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> guard(k4_img_list_lock);
+    auto& T = k4_img_list_tmp[k4_device_ordinal()];
+    hipError_t e;
+    if (!T.ev && (e = hipEventCreateWithFlags(&T.ev, hipEventDisableTiming)) != hipSuccess) return (int)e;
+    if (T.n < nb) {
+        if (T.buf) (void)hipFree(T.buf);                   // (synchronises the device: no launch still reads it)
+        T.buf = nullptr; T.n = 0;
+        int64_t want = 1024;
+        while (want < nb) want *= 2;
+        if ((e = hipMalloc((void**)&T.buf, (size_t)want * sizeof(uint32_t))) != hipSuccess) return (int)e;
+        T.n = want;
+    } else if ((e = hipStreamWaitEvent(st, T.ev, 0)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k4_img_list_count_kernel, dim3((unsigned)nb), dim3(K4_IMG_LIST_THREADS), 0, st, flags - shift, shift, nvox, T.buf);
+    hipLaunchKernelGGL(k4_img_list_scan_kernel, dim3(1), dim3(K4_IMG_LIST_THREADS), 0, st, T.buf, nb, (nb + K4_IMG_LIST_THREADS - 1) / K4_IMG_LIST_THREADS, counter);
+    hipLaunchKernelGGL(k4_img_list_write_kernel, dim3((unsigned)nb), dim3(K4_IMG_LIST_THREADS), 0, st, flags - shift, shift, nvox, T.buf, idx_out, cap);
+    const int rc = k4_check_launch();
+    if (rc) return rc;
+    return (int)hipEventRecord(T.ev, st);
+}
+//   take: entry k < n of the list -> values_out[ch * cap + k] = scratch[idx[k]][ch] (the message's [C][cap] layout), sums and flag cleared behind it: called with
+//         the full list it leaves the workspace all-zero.  An index outside [0, nvox) is skipped.
+__global__ __launch_bounds__(K4_OPT_THREADS) void k4_img_take_kernel(float* __restrict__ scratch, uint8_t* __restrict__ flags, int C, int64_t nvox,
+                                                                      const int32_t* __restrict__ idx, int64_t n, int64_t cap, float* __restrict__ values) {
+    const int64_t k = (int64_t)blockIdx.x * K4_OPT_THREADS + threadIdx.x;
+    if (k >= n) return;
+    const int64_t v = idx[k];
+    if (v < 0 || v >= nvox) return;
+    float* const s = scratch + v * C;
+    for (int ch = 0; ch < C; ++ch) {
+        values[(int64_t)ch * cap + k] = s[ch];
+        s[ch] = 0.f;
+    }
+    flags[v] = 0;
+}
+extern "C" int k4_scatter_image_take(void* workspace, int32_t C, int32_t X, int32_t Y, int32_t Z, const int32_t* idx, int64_t n, int64_t cap, float* values_out,
+                                     void* stream) {
+    if (!workspace || (((uintptr_t)workspace) & 15) || C <= 1 || C > 32 || X <= 0 || Y <= 0 || Z <= 0 || n < 0 || n > cap) return K4_ERR_BAD_ARG;
+    if (n == 0) return K4_OK;
+    if (!idx || !values_out) return K4_ERR_BAD_ARG;
+    const int64_t nvox = (int64_t)X * Y * Z;
+    const int64_t blocks = (n + K4_OPT_THREADS - 1) / K4_OPT_THREADS;
+    if (blocks > 0x7fffffffLL) return K4_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k4_img_take_kernel, dim3((unsigned)blocks), dim3(K4_OPT_THREADS), 0, (hipStream_t)stream, (float*)workspace, (uint8_t*)workspace + nvox * C * 4,
+                       C, nvox, idx, n, cap, values_out);
+    return k4_check_launch();
+}
+//   add:  ONE rank's list into the image: scratch[idx[k]][ch] += values[ch * cap + k] * scale, flag raised.  The indices of one list are distinct: plain
+//         read-modify-write.  The product rounds on its own (__fmul_rn, then __fadd_rn: never one fma) -- the dense form of the exchange computes
+//         index_add_(values * scale), and the two forms give the same bits.  An index outside [0, nvox) is skipped.
+__global__ __launch_bounds__(K4_OPT_THREADS) void k4_img_add_kernel(float* __restrict__ scratch, uint8_t* __restrict__ flags, int C, int64_t nvox,
+                                                                     const int32_t* __restrict__ idx, const float* __restrict__ values, int64_t n, int64_t cap, float scale) {
+    const int64_t k = (int64_t)blockIdx.x * K4_OPT_THREADS + threadIdx.x;
+    if (k >= n) return;
+    const int64_t v = idx[k];
+    if (v < 0 || v >= nvox) return;
+    float* const s = scratch + v * C;
+    for (int ch = 0; ch < C; ++ch) {
+        const float p = __fmul_rn(values[(int64_t)ch * cap + k], scale);
+        s[ch] = __fadd_rn(s[ch], p);
+    }
+    flags[v] = 1;
+}
+extern "C" int k4_scatter_image_add(void* workspace, int32_t C, int32_t X, int32_t Y, int32_t Z, const int32_t* idx, const float* values, int64_t n, int64_t cap,
+                                    float scale, void* stream) {
+    if (!workspace || (((uintptr_t)workspace) & 15) || C <= 1 || C > 32 || X <= 0 || Y <= 0 || Z <= 0 || n < 0 || n > cap) return K4_ERR_BAD_ARG;
+    if (n == 0) return K4_OK;
+    if (!idx || !values) return K4_ERR_BAD_ARG;
+    const int64_t nvox = (int64_t)X * Y * Z;
+    const int64_t blocks = (n + K4_OPT_THREADS - 1) / K4_OPT_THREADS;
+    if (blocks > 0x7fffffffLL) return K4_ERR_BAD_ARG;
+    hipLaunchKernelGGL(k4_img_add_kernel, dim3((unsigned)blocks), dim3(K4_OPT_THREADS), 0, (hipStream_t)stream, (float*)workspace, (uint8_t*)workspace + nvox * C * 4,
+                       C, nvox, idx, values, n, cap, scale);
     return k4_check_launch();
 }
 extern "C" int k4_adam_upd_with_perlr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -20,7 +20,12 @@ dense while a patch touches well under 1 % of it -- they use ``sparse_grad_allre
 backward touched to (int32 index, values) lists, ONE all-gather of the padded lists moves them, and every rank adds all
 lists into its dense gradient in RANK order, so the replicas hold bit-identical gradients (and MaskedAdam's "skip voxels
 with zero gradient" sees the union of the touched voxels).  Pure torch.distributed plumbing: RCCL on the GPUs, gloo in the
-CPU tests.
+CPU tests.  In the iterations without total variation (after tv_before) k0 has no dense gradient to begin with: the lookups'
+backward stops after its scatter, and the same message is built from the scatter's scratch image -- k4_scatter_image_list
+(the flagged voxels in ascending order, one byte read per voxel), k4_scatter_image_take (their sums into the message, the
+image cleared) -- and after the same all-gather every rank's list is added back into the image in rank order
+(k4_scatter_image_add), where MaskedAdam steps the union of the touched voxels in place (lib/grid.GridGrad.exchange;
+``_SPARSE_IMAGE_EXCHANGE = False`` is the A/B switch).  The iterations with total variation exchange dense gradients as before.
 """
 import torch
 import torch.distributed as dist
@@ -35,6 +40,7 @@ _TV_SEED = True     # False: dense total variation added after the backward pass
 _FUSED_LOSSES = True     # False: the elementwise loss terms as tensor-library ops (A/B, tests; CPU tensors always)
 _SPLIT_GRID_STEP = True      # False: k0's optimizer step of an iteration with a dense TV term in one pass after the backward pass (A/B, tests)
 _SPARSE_GRID_GRAD = True     # False: k0's gradient as a dense tensor in the iterations without TV too (A/B, tests)
+_SPARSE_IMAGE_EXCHANGE = True    # False: ... whenever a gradient exchange runs (data parallelism), which then lists the touched voxels of the dense tensor (A/B, tests)
 
 SPARSE_MIN_NUMEL = 1 << 20          # tensors at least this large are exchanged as (index, value) lists
 
@@ -45,7 +51,8 @@ def _world(group):
 
 def _exchange_runs(group):
     """Does a gradient exchange run this iteration?  In a job of several ranks -- and in the one-rank RCCL smoke test (_native.FORCE_COLLECTIVES).  THE predicate: the
-    routes that keep a grid's gradient out of a dense ``.grad`` (JointTrainer.step) are taken only when it says no, and every exchange runs only when it says yes."""
+    seeded routes that keep a grid's gradient out of a dense ``.grad`` (JointTrainer.step) are taken only when it says no (the 'sparse' route has an exchange of its
+    own: _SPARSE_IMAGE_EXCHANGE), and every exchange runs only when it says yes."""
     return sr_train.collectives_run(_world(group))
 
 
@@ -76,44 +83,78 @@ def sparse_grad_allreduce(params, group=None, average=True):
     if not _exchange_runs(group):
         return stats
     for p in params:
-        C = p.shape[1] if p.dim() == 5 else 1
-        if p.grad is None:
-            p.grad = torch.zeros_like(p)
-        g = p.grad.view(C, -1)
-        V = g.shape[1]
-        assert V < 2 ** 31
-        idx = touched_voxels(g)
-        n = torch.tensor([idx.numel()], dtype=torch.int64, device=g.device)
-        counts = [torch.zeros_like(n) for _ in range(world)]
-        dist.all_gather(counts, n, group=group)
-        counts = [int(c) for c in counts]
-        cap = max(max(counts), 1)
-        # one message per rank: [cap] int32 indices followed by the bits of the [C][cap] fp32 values (integer buffers: plain byte moves)
-        send = torch.zeros([(C + 1) * cap], dtype=torch.int32, device=g.device)
-        send[:idx.numel()] = idx
-        send[cap:].view(torch.float32).view(C, cap)[:, :idx.numel()] = g[:, idx.long()]
-        recv = torch.empty([world * (C + 1) * cap], dtype=torch.int32, device=g.device)
-        dist.all_gather_into_tensor(recv, send, group=group)
-        g[:, idx.long()] = 0                                     # own contribution comes back with the others, in rank order
-        scale = 1.0 / world if average else 1.0
-        for r in range(world):
-            msg = recv[r * (C + 1) * cap:(r + 1) * (C + 1) * cap]
-            ri = msg[:counts[r]].long()
-            g.index_add_(1, ri, msg[cap:].view(torch.float32).view(C, cap)[:, :counts[r]] * scale)
-        stats['bytes_gathered'] += recv.numel() * 4
-        stats['touched'].append((counts, V))
+        nbytes, touched = _list_exchange(p, group, world, average)
+        stats['bytes_gathered'] += nbytes
+        stats['touched'].append(touched)
     return stats
 
 
+def _list_exchange(p, group, world, average=True):
+    """One dense grid gradient through the (index, value) lists: -> (bytes gathered, (the ranks' counts, voxels))."""
+    C = p.shape[1] if p.dim() == 5 else 1
+    if p.grad is None:
+        p.grad = torch.zeros_like(p)
+    g = p.grad.view(C, -1)
+    V = g.shape[1]
+    assert V < 2 ** 31
+    idx = touched_voxels(g)
+    n = torch.tensor([idx.numel()], dtype=torch.int64, device=g.device)
+    counts = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(counts, n, group=group)
+    counts = [int(c) for c in counts]
+    cap = max(max(counts), 1)
+    # one message per rank: [cap] int32 indices followed by the bits of the [C][cap] fp32 values (integer buffers: plain byte moves)
+    send = torch.zeros([(C + 1) * cap], dtype=torch.int32, device=g.device)
+    send[:idx.numel()] = idx
+    send[cap:].view(torch.float32).view(C, cap)[:, :idx.numel()] = g[:, idx.long()]
+    recv = torch.empty([world * (C + 1) * cap], dtype=torch.int32, device=g.device)
+    dist.all_gather_into_tensor(recv, send, group=group)
+    g[:, idx.long()] = 0                                     # own contribution comes back with the others, in rank order
+    scale = 1.0 / world if average else 1.0
+    for r in range(world):
+        msg = recv[r * (C + 1) * cap:(r + 1) * (C + 1) * cap]
+        ri = msg[:counts[r]].long()
+        g.index_add_(1, ri, msg[cap:].view(torch.float32).view(C, cap)[:, :counts[r]] * scale)
+    return recv.numel() * 4, (counts, V)
+
+
+def _image_exchange_grids(model):
+    """The grids whose gradient of this iteration travels from the scatter's scratch image: those JointTrainer.step armed 'sparse' -- a function of the
+    configuration and global_step alone, hence the same on every rank (what a rank's backward did or did not leave behind must not decide which collectives
+    it enters: they would stop matching and the job would hang)."""
+    out = []
+    for m in model.modules():
+        route = m.__dict__.get('_k4_route')
+        if route is not None and route.route == 'sparse':
+            out.append(m)
+    return out
+
+
 def exchange_gradients(model, net_sr, group=None):
-    """Data-parallel gradient exchange of the joint step: big grids sparse, everything else in one dense bucket."""
+    """Data-parallel gradient exchange of the joint step: a grid armed 'sparse' from its scratch image (lib/grid.GridGrad.exchange: no dense gradient on either
+    side of it), the other big grids as lists from their dense gradients, everything else in one dense bucket."""
     if not _exchange_runs(group):
         return {'world': 1}
-    everything = [p for p in list(model.parameters()) + list(net_sr.parameters()) if p.requires_grad]
+    world = _world(group)
+    image = {'image_bytes_gathered': 0, 'image_touched': []}
+    taken = set()
+    for owner in _image_exchange_grids(model):
+        one = owner.grad_route.exchange(group)
+        if one is None:
+            # this rank's gradient is a dense tensor after all (no scratch image, a `.grad` from elsewhere): the same two collectives, the same
+            # message, built from and merged into that tensor
+            nbytes, touched = _list_exchange(owner.grid, group, world)
+            one = {'bytes_gathered': nbytes, 'touched': touched}
+        image['image_bytes_gathered'] += one['bytes_gathered']
+        image['image_touched'].append(one['touched'])
+        taken.add(id(owner.grid))
+    # (a grid exchanged above is in neither list: sparse_grad_allreduce would give it a dense zero `.grad`)
+    everything = [p for p in list(model.parameters()) + list(net_sr.parameters()) if p.requires_grad and id(p) not in taken]
     big = [p for p in everything if p.numel() >= SPARSE_MIN_NUMEL and p.dim() == 5]
     big_ids = {id(p) for p in big}
     small = [p for p in everything if id(p) not in big_ids]
     stats = sparse_grad_allreduce(big, group=group)
+    stats.update(image)
     stats['bytes_dense'] = sr_train.allreduce_gradients(small, group=group)
     return stats
 
@@ -335,7 +376,10 @@ class JointTrainer:
         #   this iteration's backward pass and the next iteration's lookup.
         # 'sparse': without TV (after tv_before: 290,000 of fern_lg_joint_l1's 300,000 iterations) the lookups' backward is the only contribution to k0's gradient and
         #   MaskedAdam skips voxels without one: the backward stops after its scatter and the optimizer updates the touched voxels from there -- no dense 1.36 GB gradient.
-        # All three only when no gradient exchange runs: it reads the dense gradient and sends the TOUCHED voxels, which a dense seed would make all of them.
+        # The two seeded routes only when no gradient exchange runs: it reads the dense gradient and sends the TOUCHED voxels, which a dense seed would make all of them.
+        # 'sparse' under an exchange too (_SPARSE_IMAGE_EXCHANGE): the scratch image already is the exchange's message -- a flag byte per touched voxel, its sums as C
+        #   consecutive floats -- so exchange_gradients sends the lists from there and merges the ranks' lists back into it in rank order (GridGrad.exchange), and
+        #   the in-place step runs over the union.  The arming depends on the configuration and global_step only: every rank takes the same collectives.
         seed_tv = tv_now and self._dense_tv_ahead(global_step)
         armed, seeded = [], []
 
@@ -351,7 +395,7 @@ class JointTrainer:
                         arm(grid, 'split' if grid in owners else 'dense')
                         fn(weight / self.n_train_images, 'seed')
                         seeded.append(grid)
-            elif _SPARSE_GRID_GRAD and not tv_now and not _exchange_runs(self.group):
+            elif _SPARSE_GRID_GRAD and not tv_now and (not _exchange_runs(self.group) or _SPARSE_IMAGE_EXCHANGE):
                 for grid in self._sparse_grid_owners():
                     arm(grid, 'sparse')
             split = [g for g in seeded if g in owners] if seed_tv else []

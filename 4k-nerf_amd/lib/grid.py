@@ -180,6 +180,7 @@ class GridGrad:
         backward:  'sparse' without a seed, or early: the scatter's sums stay in the device's scratch image, which this object then holds;
                    otherwise a dense gradient (zeros or the seed, + scatter + sweep) is returned to autograd
         close():   a seed no backward consumed becomes (or is added to) ``.grad``
+        exchange(): data parallelism, route 'sparse': the image's sums are replaced by the ranks' averaged sums over the union of their voxels (in place)
         optimizer: image() + consumed() around its in-place step / sweep() into a dense ``.grad``
         abort():   from any state back to idle; nothing of this iteration reaches the next one
     """
@@ -320,6 +321,64 @@ class GridGrad:
         _, C_, X, Y, Z = g.shape
         img.run(lambda: N.check(N.lib().k4_grid_sample_3d_backward_cl_sweep(C_, X, Y, Z, N.ptr(img.ws), N.f32(g.grad), N.stream()), 'grid_sample_3d_backward_cl_sweep'))
         img.holder, self.sums = None, False
+
+    def exchange(self, group=None, average=True):
+        """Data-parallel exchange of a gradient that stayed in the scratch image (route 'sparse' under joint_train.exchange_gradients), on the current stream:
+        the flagged voxels are listed in ascending order (k4_scatter_image_list; the host reads their number -- the one synchronisation the dense form has too),
+        the ranks' counts are all-gathered, the list's sums are taken out of the image into the message of joint_train.sparse_grad_allreduce ([cap] int32 indices |
+        bits of the [C][cap] fp32 values; k4_scatter_image_take leaves the image all-zero), ONE all_gather_into_tensor moves the padded messages, and every rank's
+        list is added back in rank order (k4_scatter_image_add, scale 1 / world): the image then holds bit-identical averaged sums on every replica, its flags mark
+        the union of the ranks' voxels, and MaskedAdam._sparse_step runs as in a single-process job -- `.grad` stays None.  A rank whose backward never reached the
+        grid sends an empty list and receives like the others.  -> statistics, or None when this rank's gradient is a dense tensor after all (no scratch image,
+        a `.grad` from elsewhere: pending sums are swept into it): the caller then runs the SAME two collectives with the message built from that tensor."""
+        import torch.distributed as dist
+        g = self.owner.grid
+        _, C_, X, Y, Z = g.shape
+        if g.grad is not None:
+            if self.sums:
+                self.sweep()
+            return None
+        if self.sums:
+            img = self.image()
+        else:
+            img = _scratch_image(g.device, C_, X, Y, Z, self)
+            if img is None:
+                return None
+        L, dev, V = N.lib(), g.device, X * Y * Z
+        world = dist.get_world_size(group)
+        n = 0
+        if self.sums:
+            counter = torch.empty([1], dtype=torch.int64, device=dev)
+            room = max(1024, V // 16)
+            while True:
+                idx = torch.empty([room], dtype=torch.int32, device=dev)
+                img.run(lambda: N.check(L.k4_scatter_image_list(N.ptr(img.ws), C_, X, Y, Z, N.ptr(idx), room, N.ptr(counter), N.stream()), 'k4_scatter_image_list'))
+                n = int(counter)
+                if n <= room:
+                    break
+                room = n
+        mine = torch.tensor([n], dtype=torch.int64, device=dev)
+        counts = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(counts, mine, group=group)
+        counts = [int(c) for c in counts]
+        cap = max(max(counts), 1)
+        words = (C_ + 1) * cap
+        send = torch.zeros([words], dtype=torch.int32, device=dev)
+        if n > 0:
+            send[:n] = idx[:n]
+            img.run(lambda: N.check(L.k4_scatter_image_take(N.ptr(img.ws), C_, X, Y, Z, N.ptr(send), n, cap, N.ptr(send[cap:]), N.stream()), 'k4_scatter_image_take'))
+        recv = torch.empty([world * words], dtype=torch.int32, device=dev)
+        dist.all_gather_into_tensor(recv, send, group=group)
+        scale = 1.0 / world if average else 1.0
+
+        def add():
+            for r in range(world):
+                msg = recv[r * words:(r + 1) * words]
+                N.check(L.k4_scatter_image_add(N.ptr(img.ws), C_, X, Y, Z, N.ptr(msg), N.ptr(msg[cap:]), counts[r], cap, scale, N.stream()), 'k4_scatter_image_add')
+        img.holder = self
+        img.run(add)
+        self.sums = True
+        return {'bytes_gathered': recv.numel() * 4, 'touched': (counts, V)}
 
     def abort(self):
         """Back to idle.  After a finished iteration that only disarms.  After one the caller gave up on: the seed is forgotten (it holds a TV term of parameters a later

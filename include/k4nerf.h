@@ -37,7 +37,7 @@ extern "C" {
 #define K4_ERR_UNSUPPORTED  10002   /* configuration not covered by the fused kernel (use the staged ops) */
 
 /* ABI 16: k4_rdb_train without fused_lrelu / g5_from_gx0_add / no_join / defer_side / g5_given (aux_stream selects the launch tapes' form), k4_sft_train_bwd removed */
-#define K4_ABI_VERSION      24      /* 24: the 'patch_inmask' ray sampler's hit test (csrc/k4_staged.hip): k4_hit_coarse_geo, k4_patch_hit_counts, k4_patch_hit_entries;  23: LPIPS-VGG frame scoring (csrc/k4_lpips.hip): k4_lpips_head(+_workspace_bytes), k4_lpips_total, k4_lpips_check_frame; k4_vgg_conv3x3 takes any H, W >= 1 and pools in floor mode;  22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
+#define K4_ABI_VERSION      24      /* 24: the 'patch_inmask' ray sampler's hit test (csrc/k4_staged.hip): k4_hit_coarse_geo, k4_patch_hit_counts, k4_patch_hit_entries -- and, added without a bump because they break no caller, k4_scatter_image_list / _take / _add (csrc/k4_opt.hip: the scatter image as the data-parallel exchange's message);  23: LPIPS-VGG frame scoring (csrc/k4_lpips.hip): k4_lpips_head(+_workspace_bytes), k4_lpips_total, k4_lpips_check_frame; k4_vgg_conv3x3 takes any H, W >= 1 and pools in floor mode;  22: vector-quantised colour features (csrc/k4_vq.hip): k4_vq_project_fwd, k4_vq_project_bwd(+_workspace_bytes), k4_vq_codebook_floats, k4_vq_chunk_codes, k4_vq_prepare_codebook, k4_vq_assign(+_workspace_bytes), k4_vq_update_codebook, k4_vq_desc + k4_march_vq_fwd, k4_grid_sample_3d_backward_terms + k4_sorted_segment_add; 21: DirectBiVoxGO (lib/dbvgo.py): k4_sample_bg_pts_on_rays, k4_bivox_desc + k4_march_bivox_fwd; 20: vector-matrix factored grids (csrc/k4_tensorf.hip): k4_tensorf_sample, k4_tensorf_sample_backward, k4_tensorf_dense, k4_tensorf_tv_add_grad; 19: frame evaluation (csrc/k4_metric.hip): k4_frame_metrics, k4_frame_metrics_workspace_bytes; 18: the perceptual / style terms of the '+gan' recipes (csrc/k4_vgg.hip): k4_vgg_conv3x3, k4_vgg_pack_weight, k4_vgg_weight_bytes, k4_vgg_conv1_1 / _bwd, k4_vgg_pool_bwd, k4_vgg_l1_fwd / _bwd, k4_vgg_l1_workspace_bytes, k4_vgg_gram, k4_vgg_gram_workspace_bytes, k4_vgg_gram_bwd_pack; 17: the U-Net discriminator of the '+gan' recipes (csrc/k4_disc.hip): k4_disc_conv_s2, k4_disc_wgrad_s2, k4_bilinear2x_nhwc / _bwd_nhwc, k4_sn_prepare, k4_sn_project_grad, k4_gan_loss_fwd / _bwd; 15: k4_cumdist_thres, k4_contracted_desc + k4_march_contracted_fwd (DirectContractedVoxGO); 14: k4_sft_train_bwd_gx / k4_sft_train_bwd_rest, k4_rdb_train.aux_stream (the SFT layers' backward split into the chain's grad_x launch and the rest on a third stream), k4_grid_flag_corners / k4_masked_adam_upd_unflagged / k4_masked_adam_upd_sparse_cl_seeded (a grid's masked step in two exact parts); 13: launch tapes (k4_tape_*), k4_add_f32, k4_upsample2x_nhwc / _bwd_nhwc, k4_side_wait_main / k4_main_wait_side, k4_stream_create_overlapping / k4_streams_overlap, K4_CONV_SMALL, k4_rdb_train.no_join / defer_side, k4_sft_train_bwd_side / _main / k4_sft_train_reduce, k4_nhwc_window_to_planar, k4_rgbnet_input_mpi, k4_grid_sample_3d_backward_cl_scatter / _sweep, k4_masked_adam_upd_sparse_cl, k4_joint_losses_fwd / _bwd; 12: round-5 experiments removed (k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4, k4_repack_k0_brick4, k4_k0_brick4_floats: profiles/r05_split_path_brick_parts_removed.patch), k4_mlp_desc.arith K4_MLP_ARITH_B2; 11: k4_sft_train_bwd_ex, k4_sft_train_fwd_ex, k4_conv2d_wgrad_dbias_bf16x6_acc, k4_zero_f32, K4_EPI_LRELU_BWD, k4_rdb_train.gc_acc / gx0_add / dwdb_span / fused_lrelu / g5_from_gx0_add, k4_total_variation_add_grad dense_mode 2; 10: k4_train_select_mpi, k4_train_compact, k4_ndc_points_of (training forward with one read-back instead of four); 9: split shading path: k4_march_workspace_bytes_pre, k4_march_pre_supported, K4_K0_BRICK4 + k4_repack_k0_brick4 / k4_k0_brick4_floats; 8: k4_conv3x3_p16_sft_multi, k4_conv_sft_epilogue_bytes, k4_rdb_train_fwd / k4_rdb_train_bwd; 7: pre-split decoder activations: k4_conv3x3_p16_multi, k4_conv_weight_p16_bytes, k4_sft_nhwc_p16_multi, k4_absmax_slice; 6: k4_conv2d_sft_nhwc_bf16x6_multi removed; k4_conv2d_wgrad_dbias_bf16x6, k4_pack_conv_weight_bf16x6_multi, k4_lrelu_bwd, k4_grid_sample_3d_backward_cl, k4_touched_voxels; 5: k4_build_live_mask, k4_sft_train_*, K4_ARITH_F16X3 / k4_conv_weight_f16x3_bytes, no tile_queue, round-1 bf16x3 entry points removed; 4: marcher training entry points (k4_rgbnet_*, k4_distortion_loss); 2: SR / optimizer / ray-generation entry points, k4_mlp_desc.arith; 3: larger marcher workspace (bundle order), k4_sft_nhwc_multi arith, fused conv + SFT entry */
 int k4_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------
@@ -740,6 +740,22 @@ int k4_distortion_loss(const float* w, const float* s, const int64_t* ray_id, in
  * order: what the data-parallel exchange of the joint step sends instead of the dense tensor.  *counter (device) = the total number of
  * touched voxels, also when it exceeds `cap` (then only `cap` indices were written: retry with a larger list). */
 int k4_touched_voxels(const float* grad, int32_t channels, int64_t n_vox, int32_t* idx_out, int64_t cap, int64_t* counter, void* stream);
+
+/* The same exchange for a grid whose gradient stayed in the scratch image of k4_grid_sample_3d_backward_cl_scatter (`workspace`: scratch[n_vox][channels] fp32
+ * sums, then one flag byte per voxel at byte offset n_vox*channels*4 -- 4-byte aligned only; channels 2..32, 16-byte aligned base, as k4_masked_adam_upd_sparse_cl):
+ *   k4_scatter_image_list: the flagged voxels' indices in ASCENDING order (count pass, prefix scan, write pass: no sort, no atomics; 1 byte read per voxel and
+ *     pass), *counter (device) = their number, also when it exceeds `cap` (then the first `cap` were written) -- k4_touched_voxels's contract.  The workspace is
+ *     unchanged.  Keeps one small device buffer per device between calls.
+ *   k4_scatter_image_take: values_out[ch * cap + k] = scratch[idx[k]][ch] for k < n (the message's [channels][cap] layout; entries k >= n are left alone), those
+ *     sums and the voxel's flag cleared: with the full list the workspace is all-zero behind it.
+ *   k4_scatter_image_add: scratch[idx[k]][ch] += values[ch * cap + k] * scale (product and sum rounded separately, as index_add_(values * scale)), flag raised;
+ *     the indices of one list are distinct (no atomics).  One call per rank, in rank order, gives every replica the same bits.
+ * take and add skip an index outside [0, n_vox); n <= cap. */
+int k4_scatter_image_list(const void* workspace, int32_t channels, int32_t X, int32_t Y, int32_t Z, int32_t* idx_out, int64_t cap, int64_t* counter, void* stream);
+int k4_scatter_image_take(void* workspace, int32_t channels, int32_t X, int32_t Y, int32_t Z, const int32_t* idx, int64_t n, int64_t cap, float* values_out,
+                          void* stream);
+int k4_scatter_image_add(void* workspace, int32_t channels, int32_t X, int32_t Y, int32_t Z, const int32_t* idx, const float* values, int64_t n, int64_t cap,
+                         float scale, void* stream);
 
 /* SFTLayer of the VC-Decoder in the training graph (lib/sr_esrnet.py:112-123 under autograd, run_sr.py:869-1014):
  *   y = x * (scale + 1) + shift,   scale = W1s lrelu(W0s c + b0s) + b1s,   shift = W1h lrelu(W0h c + b0h) + b1h
