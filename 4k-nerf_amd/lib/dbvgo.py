@@ -20,8 +20,8 @@ import torch.nn as nn
 
 from .. import _native as N
 from . import grid
-from .dvgo import Raw2Alpha, Alphas2Weights, _FusedMarcher, _take, segment_sum, render_utils_cuda
-from .dcvgo import create_full_step_id
+from .dvgo import Raw2Alpha, Alphas2Weights      # noqa: F401  (names the reference's module exports)
+from .dvgo import _VoxGOCommon, _take, _rgbnet_stack, create_full_step_id, segment_sum, render_utils_cuda
 
 
 def segment_max(src, index, out):
@@ -31,7 +31,7 @@ def segment_max(src, index, out):
 
 
 '''Model'''
-class DirectBiVoxGO(nn.Module, _FusedMarcher):
+class DirectBiVoxGO(nn.Module, _VoxGOCommon):
     def __init__(self, xyz_min, xyz_max,
                  num_voxels=0, num_voxels_base=0,
                  alpha_init=None,
@@ -90,19 +90,7 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
             self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
             dim0 = (3 + 3 * viewbase_pe * 2)
             dim0 += self.k0_dim
-            self.rgbnet = nn.ModuleList([
-                nn.Sequential(
-                    nn.Linear(dim0, rgbnet_width), nn.ReLU(inplace=True),
-                    *[
-                        nn.Sequential(nn.Linear(rgbnet_width, rgbnet_width), nn.ReLU(inplace=True))
-                        for _ in range(rgbnet_depth - 2)
-                    ],
-                    nn.Linear(rgbnet_width, 3),
-                )
-                for _ in range(2)
-            ])
-            nn.init.constant_(self.rgbnet[0][-1].bias, 0)
-            nn.init.constant_(self.rgbnet[1][-1].bias, 0)
+            self.rgbnet = nn.ModuleList([_rgbnet_stack(dim0, rgbnet_width, rgbnet_depth) for _ in range(2)])
             if not bg_use_mlp:
                 self.k0[1] = new_grid(k0_type, 3, self.k0_config)
                 self.rgbnet[1] = None
@@ -164,29 +152,6 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
                 for i in range(2)
             ])
 
-    @torch.no_grad()
-    def update_occupancy_cache(self):
-        """lib/dbvgo.py:189-200: mask[i] &= maxpool3(alpha(density[i] at the mask's nodes)) > fast_color_thres, on HIP kernels."""
-        nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, list(self.mask_cache[0].mask.shape))
-        for i in range(2):
-            alpha = self.activate_density(self.density[i](nodes))
-            self.mask_cache[i].mask &= grid.occupancy_from_alpha(alpha, self.fast_color_thres)
-
-    def density_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.density[0].total_variation_add_grad(w, w, w, dense_mode)
-        self.density[1].total_variation_add_grad(w, w, w, dense_mode)
-
-    def k0_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.k0[0].total_variation_add_grad(w, w, w, dense_mode)
-        self.k0[1].total_variation_add_grad(w, w, w, dense_mode)
-
-    def activate_density(self, density, interval=None):
-        interval = interval if interval is not None else self.voxel_size_ratio
-        shape = density.shape
-        return Raw2Alpha.apply(density.flatten(), self.act_shift, interval).reshape(shape)
-
     # ------------------------------------------------------------------ sampling
     def _n_outer(self, stepsize):
         """lib/dbvgo.py:234,242: with the reference's host float32 ``stepdist.item()``."""
@@ -230,36 +195,10 @@ class DirectBiVoxGO(nn.Module, _FusedMarcher):
             step_id = step_id.view(N_, -1).index_select(0, rows).reshape(-1)
             ray_pts = ray_pts.view(N_, -1, 3).index_select(0, rows).reshape(-1, 3)
 
-        # skip known free space
-        mask = mask_grid(ray_pts)
-        ray_pts, ray_id, step_id = _take(mask, ray_pts, ray_id, step_id)
-
-        # query for alpha w/ post-activation
-        density = density_grid(ray_pts)
-        alpha = self.activate_density(density, interval)
-        if self.fast_color_thres > 0:
-            mask = (alpha > self.fast_color_thres)
-            ray_pts, ray_id, step_id, density, alpha = _take(mask, ray_pts, ray_id, step_id, density, alpha)
-
-        # compute accumulated transmittance
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N_)
-        if self.fast_color_thres > 0:
-            mask = (weights > self.fast_color_thres)
-            weights, alpha, ray_pts, ray_id, step_id = _take(mask, weights, alpha, ray_pts, ray_id, step_id)
-
-        # query for color
-        k0 = k0_grid(ray_pts)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if rgbnet is None:
-            # no view-depend effect
-            rgb = torch.sigmoid(k0)
-        else:
-            # view-dependent color emission (lib/dbvgo.py:298-304) on k4_rgbnet_fwd / _bwd
-            viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-            viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
-            rgb = self._k4_rgbnet_sigmoid(torch.cat([k0, viewdirs_emb], -1), net=rgbnet)
+        # skip known free space, alpha and weights below the threshold (lib/dbvgo.py:270-292); then the colour (lib/dbvgo.py:294-304)
+        ray_pts, ray_id, (step_id,), alpha, weights, alphainv_last, _ = self._k4_filter_samples(
+            ray_pts, ray_id, (step_id,), interval, N_, mask_grid, density_grid)
+        rgb = self._k4_shade(k0_grid(ray_pts), viewdirs, ray_id, rgbnet)
 
         return dict(
             rgb=rgb, alpha=alpha, weights=weights, alphainv_last=alphainv_last,

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from .. import _native as N
 from . import grid
-from .dvgo import Raw2Alpha, Alphas2Weights, _FusedMarcher, _take, segment_sum
+from .dvgo import Raw2Alpha, Alphas2Weights      # noqa: F401  (names the reference's module exports)
+from .dvgo import _VoxGOCommon, _take, _rgbnet_stack, create_full_step_id, segment_sum
 from . import train_ops
 
 
@@ -46,15 +47,8 @@ class _Ub360Utils:
 ub360_utils_cuda = _Ub360Utils()
 
 
-def create_full_step_id(shape, device=None):
-    """(ray_id, step_id) of every sample of an [n_rays, n_steps] table, flattened row-major (lib/dmpigo.py create_full_step_id)."""
-    ray_id = torch.arange(shape[0], device=device).view(-1, 1).expand(shape).flatten()
-    step_id = torch.arange(shape[1], device=device).view(1, -1).expand(shape).flatten()
-    return ray_id, step_id
-
-
 '''Model'''
-class DirectContractedVoxGO(nn.Module, _FusedMarcher):
+class DirectContractedVoxGO(nn.Module, _VoxGOCommon):
     def __init__(self, xyz_min, xyz_max,
                  num_voxels=0, num_voxels_base=0,
                  alpha_init=None,
@@ -123,15 +117,7 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
             self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
             dim0 = (3 + 3 * viewbase_pe * 2)
             dim0 += self.k0_dim
-            self.rgbnet = nn.Sequential(
-                nn.Linear(dim0, rgbnet_width), nn.ReLU(inplace=True),
-                *[
-                    nn.Sequential(nn.Linear(rgbnet_width, rgbnet_width), nn.ReLU(inplace=True))
-                    for _ in range(rgbnet_depth - 2)
-                ],
-                nn.Linear(rgbnet_width, 3),
-            )
-            nn.init.constant_(self.rgbnet[-1].bias, 0)
+            self.rgbnet = _rgbnet_stack(dim0, rgbnet_width, rgbnet_depth)
 
         # occupancy grid (lib/dcvgo.py:116-123)
         if mask_cache_world_size is None:
@@ -175,18 +161,7 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
         self._set_grid_resolution(num_voxels)
         self.density.scale_volume_grid(self.world_size)
         self.k0.scale_volume_grid(self.world_size)
-        if int(np.prod(self.world_size.tolist())) <= 256 ** 3:
-            nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
-            occupied = grid.occupancy_from_alpha(self.activate_density(self.density.get_dense_grid())[0, 0], self.fast_color_thres)
-            self.mask_cache = grid.MaskGrid(path=None, mask=self.mask_cache(nodes) & occupied,
-                                            xyz_min=self.xyz_min, xyz_max=self.xyz_max).to(nodes.device)
-
-    @torch.no_grad()
-    def update_occupancy_cache(self):
-        """lib/dcvgo.py:180-192: mask &= maxpool3(alpha(density at the mask's nodes)) > fast_color_thres, on HIP kernels."""
-        nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, list(self.mask_cache.mask.shape))
-        alpha = self.activate_density(self.density(nodes))
-        self.mask_cache.mask &= grid.occupancy_from_alpha(alpha, self.fast_color_thres)
+        self._k4_regrow_mask_cache()
 
     def update_occupancy_cache_lt_nviews(self, rays_o_tr, rays_d_tr, imsz, render_kwargs, maskout_lt_nviews):
         """lib/dcvgo.py:194-211: keep the voxels that at least ``maskout_lt_nviews`` training views sample (gradient of an all-ones grid > 1)."""
@@ -203,19 +178,6 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
                 count.data += (ones.grid.grad > 1)
         with torch.no_grad():
             self.mask_cache.mask &= (count >= maskout_lt_nviews)[0, 0]
-
-    def density_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.density.total_variation_add_grad(w, w, w, dense_mode)
-
-    def k0_total_variation_add_grad(self, weight, dense_mode):
-        w = weight * self.world_size.max() / 128
-        self.k0.total_variation_add_grad(w, w, w, dense_mode)
-
-    def activate_density(self, density, interval=None):
-        interval = interval if interval is not None else self.voxel_size_ratio
-        shape = density.shape
-        return Raw2Alpha.apply(density.flatten(), self.act_shift, interval).reshape(shape)
 
     # ------------------------------------------------------------------ sampling
     def _step_table(self, stepsize, device):
@@ -345,37 +307,10 @@ class DirectContractedVoxGO(nn.Module, _FusedMarcher):
         ray_pts, inner_mask, t, ray_id, step_id = _take(
             keep, ray_pts.reshape(-1, 3), inner_mask.flatten(), t[None].expand(Nr, n_max).flatten(), ray_id, step_id)
 
-        # skip known free space
-        mask = self.mask_cache(ray_pts)
-        ray_pts, inner_mask, t, ray_id, step_id = _take(mask, ray_pts, inner_mask, t, ray_id, step_id)
-
-        # query for alpha w/ post-activation
-        density = self.density(ray_pts)
-        alpha = self.activate_density(density, interval)
-        if self.fast_color_thres > 0:
-            mask = (alpha > self.fast_color_thres)
-            ray_pts, inner_mask, t, ray_id, step_id, density, alpha = _take(mask, ray_pts, inner_mask, t, ray_id, step_id, density, alpha)
-
-        # compute accumulated transmittance
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, Nr)
-        if self.fast_color_thres > 0:
-            mask = (weights > self.fast_color_thres)
-            ray_pts, inner_mask, t, ray_id, step_id, density, alpha, weights = _take(
-                mask, ray_pts, inner_mask, t, ray_id, step_id, density, alpha, weights)
-
-        # query for color
-        k0 = self.k0(ray_pts)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if self.rgbnet is None:
-            # no view-depend effect
-            rgb = torch.sigmoid(k0)
-        else:
-            # view-dependent color emission (lib/dcvgo.py:334-341) on k4_rgbnet_fwd / _bwd
-            viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-            viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
-            rgb = self._k4_rgbnet_sigmoid(torch.cat([k0, viewdirs_emb], -1))
+        # skip known free space, alpha and weights below the threshold (lib/dcvgo.py:306-328); then the colour (lib/dcvgo.py:330-341)
+        ray_pts, ray_id, (inner_mask, t, step_id), alpha, weights, alphainv_last, density = self._k4_filter_samples(
+            ray_pts, ray_id, (inner_mask, t, step_id), interval, Nr, self.mask_cache, self.density, keep_density=True)
+        rgb = self._k4_shade(self.k0(ray_pts), viewdirs, ray_id, self.rgbnet)
 
         # Ray marching
         rgb_marched = segment_sum(weights.unsqueeze(-1) * rgb, ray_id, Nr)

@@ -28,7 +28,7 @@ DEPTH_SPLIT = True              # fused marcher: depth-ordered geometry stage wh
 DEPTH_SPLIT_MIN_GAIN = 0.05     # smallest share of alpha-passing voxels behind the split in stopped columns for which the geometry stage is cut in two launches
                                 # (measured, profiles/r06_depth_split.md: the cut itself costs 0-2 % of the call at 128 / 192 of 256 samples, +4 % at 64; the opaque scene gains 10 %)
 DEPTH_SPLIT_MIN_OPAQUE = 0.5    # ... and smallest share of occupied z columns along which a ray reaches the T < 1e-3 stop (bench scene: 0.16 -> one launch; opaque wall: 1.0)      # training forward: the three sample filters decided by one launch (same values)
-from .dvgo import Raw2Alpha, Alphas2Weights, render_utils_cuda, _FusedMarcher, segment_sum, coarse_mask_on_grid, _take
+from .dvgo import Raw2Alpha, Alphas2Weights, render_utils_cuda, _VoxGOCommon, segment_sum, coarse_mask_on_grid, _view_embedding
 
 
 def depth_split_of(stats, n_samples, min_gain, min_opaque):
@@ -50,13 +50,14 @@ def _mlp(dim_in, width, depth, dim_out):
     """Linear-ReLU stack with the reference's module nesting (state-dict keys '0', '2.0', ..., lib/dmpigo.py:112-120); the last
     bias starts at 0."""
     act = nn.ReLU(inplace=True)
+    # (hidden layers drawn before the first one, unlike dvgo._rgbnet_stack: the seeded initial weights of every DirectMPIGO so far depend on it)
     hidden = [nn.Sequential(nn.Linear(width, width), act) for _ in range(depth - 2)]
     net = nn.Sequential(nn.Linear(dim_in, width), act, *hidden, nn.Linear(width, dim_out))
     nn.init.constant_(net[-1].bias, 0)
     return net
 
 
-class DirectMPIGO(torch.nn.Module, _FusedMarcher):
+class DirectMPIGO(torch.nn.Module, _VoxGOCommon):
     def __init__(self, xyz_min, xyz_max,
                  num_voxels=0, mpi_depth=0,
                  mask_cache_path=None, mask_cache_thres=1e-3, mask_cache_world_size=None,
@@ -177,21 +178,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         self._set_grid_resolution(num_voxels, mpi_depth)
         self.density.scale_volume_grid(self.world_size)
         self._scale_k0()
-        if int(np.prod(self.world_size.tolist())) <= 256 ** 3:
-            nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
-            dens = self.density.get_dense_grid() + self.act_shift.grid        # [1,1,X,Y,Z] + [1,1,1,1,D] (D == Z here)
-            occupied = grid.occupancy_from_alpha(self.activate_density(dens)[0, 0], self.fast_color_thres)
-            self.mask_cache = grid.MaskGrid(path=None, mask=self.mask_cache(nodes) & occupied,
-                                            xyz_min=self.xyz_min, xyz_max=self.xyz_max).to(nodes.device)
-
-    @torch.no_grad()
-    def update_occupancy_cache(self):
-        """lib/dmpigo.py:214-226: mask &= maxpool3(alpha(density at the mask's nodes)) > fast_color_thres.  The density lookup
-        (k4_grid_sample_3d), the activation (k4_raw2alpha) and the pooled threshold (k4_alpha_maxpool3_gt) are HIP kernels; the mask
-        tensor is updated in place, its version bump re-keys the fused marcher's occupancy summary."""
-        nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, list(self.mask_cache.mask.shape))
-        alpha = self.activate_density(self.density(nodes))
-        self.mask_cache.mask &= grid.occupancy_from_alpha(alpha, self.fast_color_thres)
+        self._k4_regrow_mask_cache(lambda: self.density.get_dense_grid() + self.act_shift.grid)      # [1,1,X,Y,Z] + [1,1,1,1,D] (D == Z here)
 
     def update_occupancy_cache_lt_nviews(self, rays_o_tr, rays_d_tr, imsz, render_kwargs, maskout_lt_nviews):
         """lib/dmpigo.py:228-246: drop voxels seen by fewer than `maskout_lt_nviews` training views.  A view "sees" a voxel when the
@@ -260,13 +247,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         assert near == 0 and far == 1                                     # lib/dmpigo.py:275
         Nr = rays_o.shape[0]
         dev = rays_o.device
-        if k4_out is not None:                  # caller-provided outputs (e.g. slices of an all-gather send buffer)
-            rgb, depth, ainv = k4_out
-            assert rgb.shape == (Nr, 3) and depth.shape == (Nr,) and ainv.shape == (Nr,)
-        else:
-            rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
-            depth = torch.empty([Nr], dtype=torch.float32, device=dev)
-            ainv = torch.empty([Nr], dtype=torch.float32, device=dev)
+        rgb, depth, ainv, ret = self._k4_ray_outputs(Nr, dev, render_depth, k4_out=k4_out)
         if k4_counters is not None:             # the counting launch adds to counters[0..4] unconditionally (include/k4nerf.h: uint64[8])
             assert (torch.is_tensor(k4_counters) and k4_counters.is_cuda and k4_counters.dtype == torch.int64 and k4_counters.is_contiguous()
                     and k4_counters.numel() >= 8), 'k4_counters: a contiguous CUDA int64 tensor of at least 8 elements'
@@ -288,9 +269,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
                 N_samples, interval, float(self.fast_color_thres), float(bg), N.ptr(ws), ws_bytes,
                 N.f32(rgb), N.f32(depth), N.f32(ainv),
                 None if k4_counters is None else N.ptr(k4_counters), N.stream()), 'k4_march_mpi_fwd')
-        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb, 'n_max': N_samples}
-        if render_depth:
-            ret['depth'] = depth
+        ret['n_max'] = N_samples
         return ret
 
     def _k4_depth_split(self, gd, n_samples, interval):
@@ -368,18 +347,8 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
         else:
             ray_pts, ray_id, step_id, N_samples, mask_inbbox = self.sample_ray(
                 rays_o=rays_o, rays_d=rays_d, near=near, far=far, stepsize=stepsize)
-            if self.mask_cache is not None:
-                mask1 = self.mask_cache(ray_pts)
-                ray_pts, ray_id, step_id = _take(mask1, ray_pts, ray_id, step_id)
-            density = self.density(ray_pts) + self.act_shift(ray_pts)
-            alpha = self.activate_density(density, interval)
-            if self.fast_color_thres > 0:
-                mask2 = (alpha > self.fast_color_thres)
-                ray_pts, ray_id, step_id, alpha = _take(mask2, ray_pts, ray_id, step_id, alpha)
-            weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, Nr)
-            if self.fast_color_thres > 0:
-                mask3 = (weights > self.fast_color_thres)
-                ray_pts, ray_id, step_id, alpha, weights = _take(mask3, ray_pts, ray_id, step_id, alpha, weights)
+            ray_pts, ray_id, (step_id,), alpha, weights, alphainv_last, _ = self._k4_filter_samples(
+                ray_pts, ray_id, (step_id,), interval, Nr, self.mask_cache, lambda p: self.density(p) + self.act_shift(p))
         vox_emb = self._k0_features(ray_pts)
         fused_in = None
         if self.rgbnet is not None and _FUSED_MLP_INPUT:                  # the 16 ops below in one launch (lib/train_ops.RgbnetInputMPI: same values)
@@ -390,9 +359,7 @@ class DirectMPIGO(torch.nn.Module, _FusedMarcher):
             rgb_raw = torch.sigmoid(vox_emb)
         else:
             pe_spa = ((ray_pts - self.xyz_min) / (self.xyz_max - self.xyz_min)).flip((-1,)) * 2 - 1
-            viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-            viewdirs_emb = viewdirs_emb[ray_id]
+            viewdirs_emb = _view_embedding(viewdirs, self.viewfreq, ray_id)
             pe_emb = (pe_spa.unsqueeze(-1) * self.posfreq).flatten(-2)
             pe_emb = torch.cat([pe_spa, pe_emb.sin(), pe_emb.cos()], -1)
             rgb_raw = self._k4_rgbnet_sigmoid(torch.cat([vox_emb, pe_emb, viewdirs_emb], -1))

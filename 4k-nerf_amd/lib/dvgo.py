@@ -36,8 +36,9 @@ def _each(m):
     return list(m) if isinstance(m, nn.ModuleList) else [m]
 
 
-class _FusedMarcher:
-    """Mixin: device-side descriptors for the fused kernels, cached per parameter version."""
+class _VoxGOCommon:
+    """Mixin of the five voxel-grid models: device-side descriptors for the fused kernels, cached per parameter version; the sample filter and
+    the shading step of the staged (training) path; the maintenance methods the models share."""
 
     def _k4_cache(self):
         if not hasattr(self, '_k4c'):
@@ -325,11 +326,16 @@ class _FusedMarcher:
 
     # ---- shared by the one-launch marchers (k4_march_contracted_fwd, k4_march_bivox_fwd, k4_march_vq_fwd)
     @staticmethod
-    def _k4_ray_outputs(n_rays, device, render_depth, n_ainv=1):
-        """-> rgb [N,3], depth [N], alphainv_last [n_ainv N] for the kernel to fill, and the dict a forward returns (depth only on request)."""
-        rgb = torch.empty([n_rays, 3], dtype=torch.float32, device=device)
-        depth = torch.empty([n_rays], dtype=torch.float32, device=device)
-        ainv = torch.empty([n_ainv * n_rays], dtype=torch.float32, device=device)
+    def _k4_ray_outputs(n_rays, device, render_depth, n_ainv=1, k4_out=None):
+        """-> rgb [N,3], depth [N], alphainv_last [n_ainv N] for the kernel to fill, and the dict a forward returns (depth only on request).
+        ``k4_out``: caller-provided (rgb, depth, alphainv_last), e.g. slices of an all-gather send buffer, instead of fresh tensors."""
+        if k4_out is not None:
+            rgb, depth, ainv = k4_out
+            assert rgb.shape == (n_rays, 3) and depth.shape == (n_rays,) and ainv.shape == (n_ainv * n_rays,)
+        else:
+            rgb = torch.empty([n_rays, 3], dtype=torch.float32, device=device)
+            depth = torch.empty([n_rays], dtype=torch.float32, device=device)
+            ainv = torch.empty([n_ainv * n_rays], dtype=torch.float32, device=device)
         ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
         if render_depth:
             ret['depth'] = depth
@@ -366,6 +372,77 @@ class _FusedMarcher:
                             '(the CPU oracle lives in oracle/ and is test infrastructure only)')
         return rays_o.float().contiguous(), rays_d.float().contiguous(), viewdirs.float().contiguous()
 
+    # ---- the staged (training) path every model shares: the three sample filters and the shading step of the reference's op sequence
+    def _k4_filter_samples(self, ray_pts, ray_id, cols, interval, n_rays, mask_grid, density_of, keep_density=False):
+        """The staged sample filter (lib/dvgo.py:352-378 and its copies in lib/dbvgo.py, lib/dcvgo.py, lib/dmpigo.py): known free space
+        (``mask_grid``, or None), then alpha > fast_color_thres, then weights > fast_color_thres, the last two only with a threshold > 0.
+        ``cols``: per-sample tensors carried through every compaction; ``density_of``: ray_pts -> raw density.
+        -> (ray_pts, ray_id, cols, alpha, weights, alphainv_last, density), all per shaded sample but alphainv_last [n_rays];
+        density is None unless ``keep_density`` (no gather on a column the caller does not return)."""
+        carry = [ray_pts, ray_id, *cols]
+        if mask_grid is not None:
+            carry = _take(mask_grid(ray_pts), *carry)
+        density = density_of(carry[0])
+        alpha = self.activate_density(density, interval)
+        if keep_density:
+            carry.append(density)
+        if self.fast_color_thres > 0:
+            *carry, alpha = _take(alpha > self.fast_color_thres, *carry, alpha)
+        weights, alphainv_last = Alphas2Weights.apply(alpha, carry[1], n_rays)
+        if self.fast_color_thres > 0:
+            *carry, alpha, weights = _take(weights > self.fast_color_thres, *carry, alpha, weights)
+        density = carry.pop() if keep_density else None
+        return carry[0], carry[1], tuple(carry[2:]), alpha, weights, alphainv_last, density
+
+    def _k4_shade(self, k0, viewdirs, ray_id, net, direct=True):
+        """The staged shading step (lib/dvgo.py:380-412): k0 features of the shaded samples -> rgb.  ``net`` None: sigmoid(k0); else
+        sigmoid(net([k0, view embedding])) -- with ``direct=False`` the first three k0 channels are a diffuse term added to the logit."""
+        if k0.dim() == 1:
+            k0 = k0.unsqueeze(-1)
+        if net is None:
+            return torch.sigmoid(k0)
+        emb = _view_embedding(viewdirs, self.viewfreq, ray_id)
+        if direct:
+            return self._k4_rgbnet_sigmoid(torch.cat([k0, emb], -1), net=net)
+        return self._k4_rgbnet_sigmoid(torch.cat([k0[:, 3:], emb], -1), k0[:, :3], net=net)
+
+    # ---- model methods the classes share as they stand (DirectMPIGO overrides the activation and the TV weights)
+    def activate_density(self, density, interval=None):
+        interval = interval if interval is not None else self.voxel_size_ratio
+        shape = density.shape
+        return Raw2Alpha.apply(density.flatten(), self.act_shift, interval).reshape(shape)
+
+    def density_total_variation_add_grad(self, weight, dense_mode):
+        '''lib/dvgo.py:268-270: isotropic TV weight scaled by max(world_size)/128.'''
+        w = weight * self.world_size.max() / 128
+        for g in _each(self.density):
+            g.total_variation_add_grad(w, w, w, dense_mode)
+
+    def k0_total_variation_add_grad(self, weight, dense_mode):
+        '''lib/dvgo.py:272-274.'''
+        w = weight * self.world_size.max() / 128
+        for g in _each(self.k0):
+            g.total_variation_add_grad(w, w, w, dense_mode)
+
+    @torch.no_grad()
+    def update_occupancy_cache(self):
+        """lib/dvgo.py:223-233: mask &= maxpool3(alpha(density at the mask's nodes)) > fast_color_thres, per (density, mask) pair.  The lookup
+        (k4_grid_sample_3d), the activation (k4_raw2alpha) and the pooled threshold (k4_alpha_maxpool3_gt) are HIP kernels; the mask is
+        updated in place, its version bump re-keys the fused marcher's occupancy summary."""
+        nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, list(_each(self.mask_cache)[0].mask.shape))
+        for dens, mc in zip(_each(self.density), _each(self.mask_cache)):
+            mc.mask &= grid.occupancy_from_alpha(self.activate_density(dens(nodes)), self.fast_color_thres)
+
+    def _k4_regrow_mask_cache(self, raw_density=None):
+        """The tail of ``scale_volume_grid`` (lib/dvgo.py:211-221): while the grid is <= 256^3 the occupancy becomes the old mask at the
+        new nodes AND max-pooled alpha > fast_color_thres (k4_alpha_maxpool3_gt).  ``raw_density``: () -> [1,1,X,Y,Z], default the density grid."""
+        if int(np.prod(self.world_size.tolist())) <= 256 ** 3:
+            nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
+            dens = self.density.get_dense_grid() if raw_density is None else raw_density()
+            occupied = grid.occupancy_from_alpha(self.activate_density(dens)[0, 0], self.fast_color_thres)
+            self.mask_cache = grid.MaskGrid(path=None, mask=self.mask_cache(nodes) & occupied,
+                                            xyz_min=self.xyz_min, xyz_max=self.xyz_max).to(nodes.device)
+
 
 '''Model'''
 def _take(mask, *ts):
@@ -375,7 +452,33 @@ def _take(mask, *ts):
     return [t.index_select(0, i) for t in ts]
 
 
-class DirectVoxGO(torch.nn.Module, _FusedMarcher):
+def create_full_step_id(shape, device=None):
+    """(ray_id, step_id) of every sample of an [n_rays, n_steps] table, flattened row-major (lib/dmpigo.py create_full_step_id)."""
+    ray_id = torch.arange(shape[0], device=device).view(-1, 1).expand(shape).flatten()
+    step_id = torch.arange(shape[1], device=device).view(1, -1).expand(shape).flatten()
+    return ray_id, step_id
+
+
+def _view_embedding(viewdirs, viewfreq, ray_id):
+    """[v, sin(v f), cos(v f)] of every ray's view direction, gathered per sample (lib/dvgo.py:397-402)."""
+    emb = (viewdirs.unsqueeze(-1) * viewfreq).flatten(-2)
+    emb = torch.cat([viewdirs, emb.sin(), emb.cos()], -1)
+    return emb.flatten(0, -2)[ray_id]
+
+
+def _rgbnet_stack(dim0, width, depth):
+    """The colour MLP with the reference's module nesting (state-dict keys '0', '2.0', ..., lib/dvgo.py:110-124), its layers constructed
+    in written order (the order of the seeded initial weights); the last bias starts at 0."""
+    net = nn.Sequential(
+        nn.Linear(dim0, width), nn.ReLU(inplace=True),
+        *[nn.Sequential(nn.Linear(width, width), nn.ReLU(inplace=True)) for _ in range(depth - 2)],
+        nn.Linear(width, 3),
+    )
+    nn.init.constant_(net[-1].bias, 0)
+    return net
+
+
+class DirectVoxGO(torch.nn.Module, _VoxGOCommon):
     def __init__(self, xyz_min, xyz_max,
                  num_voxels=0, num_voxels_base=0,
                  alpha_init=None,
@@ -438,15 +541,7 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
             dim0 = (3 + 3 * viewbase_pe * 2)
             dim0 += self.k0_dim if rgbnet_direct else self.k0_dim - 3
             self.dim0 = dim0
-            self.rgbnet = nn.Sequential(
-                nn.Linear(dim0, rgbnet_width), nn.ReLU(inplace=True),
-                *[
-                    nn.Sequential(nn.Linear(rgbnet_width, rgbnet_width), nn.ReLU(inplace=True))
-                    for _ in range(rgbnet_depth - 2)
-                ],
-                nn.Linear(rgbnet_width, 3),
-            )
-            nn.init.constant_(self.rgbnet[-1].bias, 0)
+            self.rgbnet = _rgbnet_stack(dim0, rgbnet_width, rgbnet_depth)
 
         # occupancy grid (lib/dvgo.py:130-150)
         self.mask_cache_path = mask_cache_path
@@ -508,18 +603,7 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
         self._set_grid_resolution(num_voxels)
         self.density.scale_volume_grid(self.world_size)
         self.k0.scale_volume_grid(self.world_size)
-        if int(np.prod(self.world_size.tolist())) <= 256 ** 3:
-            nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, self.world_size.tolist())
-            occupied = grid.occupancy_from_alpha(self.activate_density(self.density.get_dense_grid())[0, 0], self.fast_color_thres)
-            self.mask_cache = grid.MaskGrid(path=None, mask=self.mask_cache(nodes) & occupied,
-                                            xyz_min=self.xyz_min, xyz_max=self.xyz_max).to(nodes.device)
-
-    @torch.no_grad()
-    def update_occupancy_cache(self):
-        """lib/dvgo.py:223-233: mask &= maxpool3(alpha(density at the mask's nodes)) > fast_color_thres, on HIP kernels."""
-        nodes = grid.grid_nodes(self.xyz_min, self.xyz_max, list(self.mask_cache.mask.shape))
-        alpha = self.activate_density(self.density(nodes))
-        self.mask_cache.mask &= grid.occupancy_from_alpha(alpha, self.fast_color_thres)
+        self._k4_regrow_mask_cache()
 
     def voxel_count_views(self, rays_o_tr, rays_d_tr, imsz, near, far, stepsize, downrate=1, irregular_shape=False):
         """lib/dvgo.py:235-268: per voxel, the number of training views whose rays pass it (gradient of an all-ones grid > 1)."""
@@ -548,21 +632,6 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
             with torch.no_grad():
                 count += (ones.grid.grad > 1)
         return count
-
-    def density_total_variation_add_grad(self, weight, dense_mode):
-        '''lib/dvgo.py:268-270: isotropic TV weight scaled by max(world_size)/128.'''
-        w = weight * self.world_size.max() / 128
-        self.density.total_variation_add_grad(w, w, w, dense_mode)
-
-    def k0_total_variation_add_grad(self, weight, dense_mode):
-        '''lib/dvgo.py:272-274.'''
-        w = weight * self.world_size.max() / 128
-        self.k0.total_variation_add_grad(w, w, w, dense_mode)
-
-    def activate_density(self, density, interval=None):
-        interval = interval if interval is not None else self.voxel_size_ratio
-        shape = density.shape
-        return Raw2Alpha.apply(density.flatten(), self.act_shift, interval).reshape(shape)
 
     @torch.no_grad()
     def hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
@@ -622,13 +691,7 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
                        k4_img_w=0, k4_counters=None, k4_out=None, k4_ws_slot=0, k4_live_mask=True, **_ignored):
         Nr = rays_o.shape[0]
         dev = rays_o.device
-        if k4_out is not None:                  # caller-provided outputs (e.g. slices of an all-gather send buffer)
-            rgb, depth, ainv = k4_out
-            assert rgb.shape == (Nr, 3) and depth.shape == (Nr,) and ainv.shape == (Nr,)
-        else:
-            rgb = torch.empty([Nr, 3], dtype=torch.float32, device=dev)
-            depth = torch.empty([Nr], dtype=torch.float32, device=dev)
-            ainv = torch.empty([Nr], dtype=torch.float32, device=dev)
+        rgb, depth, ainv, ret = self._k4_ray_outputs(Nr, dev, render_depth, k4_out=k4_out)
         if k4_counters is not None:             # the counting launch adds to counters[0..4] unconditionally (include/k4nerf.h: uint64[8])
             assert (torch.is_tensor(k4_counters) and k4_counters.is_cuda and k4_counters.dtype == torch.int64 and k4_counters.is_contiguous()
                     and k4_counters.numel() >= 8), 'k4_counters: a contiguous CUDA int64 tensor of at least 8 elements'
@@ -647,9 +710,6 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
         md, gd, stepdist, interval, act_shift, depth_n, max_steps = self._k4_plan(
             'dvgo', (float(stepsize), use_live, float(self.fast_color_thres), float(self.voxel_size), float(self.voxel_size_ratio)), build)
         if Nr == 0:
-            ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
-            if render_depth:
-                ret['depth'] = depth
             return ret
         ws, ws_bytes = self._k4_workspace(Nr, k4_img_w, max_steps, dev, k4_ws_slot)
         N.check(N.lib().k4_march_dvgo_fwd(
@@ -657,9 +717,6 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
             float(near), 1e9, stepdist, max_steps, depth_n, act_shift, interval,
             float(self.fast_color_thres), float(bg), N.ptr(ws), ws_bytes, N.f32(rgb), N.f32(depth), N.f32(ainv),
             None if k4_counters is None else N.ptr(k4_counters), N.stream()), 'k4_march_dvgo_fwd')
-        ret = {'alphainv_last': ainv, 'rgb_marched': rgb, 'rgb_feature': rgb}
-        if render_depth:
-            ret['depth'] = depth
         return ret
 
     def _forward_staged(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, **_ignored):
@@ -669,33 +726,9 @@ class DirectVoxGO(torch.nn.Module, _FusedMarcher):
         ray_pts, ray_id, step_id, _, N_samples = self.sample_ray(
             rays_o=rays_o, rays_d=rays_d, near=near, far=far, stepsize=stepsize)
         interval = stepsize * self.voxel_size_ratio
-        if self.mask_cache is not None:
-            mask1 = self.mask_cache(ray_pts)
-            ray_pts, ray_id, step_id = _take(mask1, ray_pts, ray_id, step_id)
-        density = self.density(ray_pts)
-        alpha = self.activate_density(density, interval)
-        if self.fast_color_thres > 0:
-            mask2 = (alpha > self.fast_color_thres)
-            ray_pts, ray_id, step_id, alpha = _take(mask2, ray_pts, ray_id, step_id, alpha)
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, Nr)
-        if self.fast_color_thres > 0:
-            mask3 = (weights > self.fast_color_thres)
-            ray_pts, ray_id, step_id, alpha, weights = _take(mask3, ray_pts, ray_id, step_id, alpha, weights)
-        k0 = self.k0(ray_pts)
-        if k0.dim() == 1:
-            k0 = k0.unsqueeze(-1)
-        if self.rgbnet is None:
-            rgb_raw = torch.sigmoid(k0)
-        else:
-            if self.rgbnet_direct:
-                k0_view = k0
-            else:
-                k0_view = k0[:, 3:]
-                k0_diffuse = k0[:, :3]
-            viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-            viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-            viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
-            rgb_raw = self._k4_rgbnet_sigmoid(torch.cat([k0_view, viewdirs_emb], -1), None if self.rgbnet_direct else k0_diffuse)
+        ray_pts, ray_id, (step_id,), alpha, weights, alphainv_last, _ = self._k4_filter_samples(
+            ray_pts, ray_id, (step_id,), interval, Nr, self.mask_cache, self.density)
+        rgb_raw = self._k4_shade(self.k0(ray_pts), viewdirs, ray_id, self.rgbnet, direct=self.rgbnet_direct)
         rgb_feature = segment_sum(weights.unsqueeze(-1) * rgb_raw, ray_id, Nr)
         rgb_marched = rgb_feature
         rgb_marched += (alphainv_last.unsqueeze(-1) * bg)                 # aliases rgb_feature (lib/dvgo.py:425-427)
