@@ -311,6 +311,11 @@ _EXTRA_SIGS = {
     'k4_sorted_segment_add': ([_P, _P, _I64, _I64, _P, _P], C.c_int),
     'k4_march_vq_fwd': ([C.POINTER(VqDesc), _P], C.c_int),
     'k4_patch_hit_entries': ([_I32, _I32, _I32], C.c_int64),
+    'k4_count_views_walk': ([_P, _P, _I64, _P, _P, _I32, _I32, _I32, _F, _F, _I32, _P, _P], C.c_int),
+    'k4_count_views_finalise': ([_P, _P, _I64, _P], C.c_int),
+    'k4_near_cam_mask': ([_P, _P, _P, _I32, _I32, _I32, _P, _I32, _F, _P, _P], C.c_int),
+    'k4_frustum_bounds': ([_P, _P, _P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P], C.c_int),
+    'k4_coarse_geo_bounds': ([_P, _I32, _I32, _I32, _F, _F, _F, _P, _P], C.c_int),
     'k4_frame_metrics': ([_P, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(C.c_double), _I32, C.c_double, C.c_double, _P, _P, _P, _P], C.c_int),
 }
 

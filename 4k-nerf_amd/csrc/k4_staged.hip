@@ -7,6 +7,7 @@
 #include "k4_common.h"
 #include "k4_vq.h"
 #include "k4_ray_walk.h"
+#include "k4_staged_ops.h"
 
 #define K4_THREADS 256
 static inline unsigned k4_blocks(int64_t n) { return (unsigned)((n + K4_THREADS - 1) / K4_THREADS); }
@@ -32,30 +33,12 @@ __device__ __forceinline__ uint8_t k4s_maskcache(const uint8_t* __restrict__ wor
         v = world[((size_t)a * sj + b) * sk + c] != 0;
     return v;
 }
-// corner indices / weights of F.grid_sample(bilinear, align_corners=True, zero padding) on an [X][Y][Z] grid
-__device__ __forceinline__ void k4s_grid_corners(float x, float y, float z, const float* __restrict__ mn, const float* __restrict__ mx,
-                                                 int X, int Y, int Z, size_t (&idx)[8], float (&w)[8]) {
-    const float nx = k4_norm_coord(x, mn[0], mx[0]);
-    const float ny = k4_norm_coord(y, mn[1], mx[1]);
-    const float nz = k4_norm_coord(z, mn[2], mx[2]);
-    const K4Tri t = k4_tri_setup(k4_unnorm(nx, X), k4_unnorm(ny, Y), k4_unnorm(nz, Z));
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int xx = t.x0 + K4_CX(c), yy = t.y0 + K4_CY(c), zz = t.z0 + K4_CZ(c);
-        const bool ok = (unsigned)xx < (unsigned)X && (unsigned)yy < (unsigned)Y && (unsigned)zz < (unsigned)Z;
-        idx[c] = ok ? ((size_t)xx * Y + yy) * Z + zz : 0;
-        w[c] = ok ? t.w[c] : 0.f;
-    }
-}
+// (k4s_grid_corners, k4s_raw2alpha and k4s_ray_of_pixel: k4_staged_ops.h, shared with k4_prep.hip)
 __device__ __forceinline__ float k4s_grid_blend(const float* __restrict__ g, const size_t (&idx)[8], const float (&w)[8]) {
     float v = 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) v += g[idx[c]] * w[c];
     return v;
-}
-__device__ __forceinline__ void k4s_raw2alpha(float den, float shift, float iv, float& e, float& al) {
-    e = expf(den + shift);
-    al = (iv == 1.f) ? 1.f - 1.f / (1.f + e) : 1.f - powf(1.f + e, -iv);
 }
 
 // ---------------------------------------------------------------- sample_ndc_pts_on_rays (.cu:245-270)
@@ -607,37 +590,10 @@ __global__ void k_rays_of_view(int H, int W, const float* __restrict__ Kd, const
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (int64_t)H * W) return;
     const int row = (int)(p / W), col = (int)(p - (int64_t)row * W);
-    const k4_cptr K = k4_const(Kd), M = k4_const(c2w);          // uniform: scalar loads
-    const float i = (float)(flip_x ? W - 1 - col : col) + pix_off;
-    const float j = (float)(flip_y ? H - 1 - row : row) + pix_off;
-    float d[3];
-    d[0] = __fdiv_rn(__fsub_rn(i, K[2]), K[0]);
-    d[1] = __fdiv_rn(__fsub_rn(j, K[5]), K[4]);
-    d[2] = 1.f;
-    if (!inverse_y) { d[1] = -d[1]; d[2] = -1.f; }
-    float v[3], o[3];
+    float o[3], v[3], u[3];                                      // K, c2w uniform: scalar loads
+    k4s_ray_of_pixel(row, col, H, W, k4_const(Kd), k4_const(c2w), ndc, inverse_y, flip_x, flip_y, pix_off, c_w, c_h, o, v, u);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {                                // torch.sum(dirs[..., None, :] * c2w[:3,:3], -1)
-        v[a] = __fadd_rn(__fadd_rn(__fmul_rn(d[0], M[a * 4 + 0]), __fmul_rn(d[1], M[a * 4 + 1])), __fmul_rn(d[2], M[a * 4 + 2]));
-        o[a] = M[a * 4 + 3];
-    }
-    const float nrm = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(v[0], v[0]), __fmul_rn(v[1], v[1])), __fmul_rn(v[2], v[2])));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) vd[p * 3 + a] = __fdiv_rn(v[a], nrm);
-    if (ndc) {                                                   // ndc_rays, near = 1 (lib/dvgo.py:557-574)
-        const float t = __fdiv_rn(-__fadd_rn(1.f, o[2]), v[2]);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) o[a] = __fadd_rn(o[a], __fmul_rn(t, v[a]));
-        const float o0 = __fdiv_rn(__fmul_rn(c_w, o[0]), o[2]);
-        const float o1 = __fdiv_rn(__fmul_rn(c_h, o[1]), o[2]);
-        const float o2 = __fadd_rn(1.f, __fdiv_rn(2.f, o[2]));
-        const float d0 = __fmul_rn(c_w, __fsub_rn(__fdiv_rn(v[0], v[2]), __fdiv_rn(o[0], o[2])));
-        const float d1 = __fmul_rn(c_h, __fsub_rn(__fdiv_rn(v[1], v[2]), __fdiv_rn(o[1], o[2])));
-        const float d2 = __fdiv_rn(-2.f, o[2]);
-        o[0] = o0; o[1] = o1; o[2] = o2; v[0] = d0; v[1] = d1; v[2] = d2;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { ro[p * 3 + a] = o[a]; rd[p * 3 + a] = v[a]; }
+    for (int a = 0; a < 3; ++a) { ro[p * 3 + a] = o[a]; rd[p * 3 + a] = v[a]; vd[p * 3 + a] = u[a]; }
 }
 
 // ---------------------------------------------------------------- ub360_utils_cuda.cumdist_thres (lib/cuda/ub360_utils_kernel.cu:12-32)
@@ -1151,9 +1107,7 @@ extern "C" int k4_get_rays_of_a_view(int32_t H, int32_t W, const float* K_dev, c
                                      int32_t inverse_y, int32_t flip_x, int32_t flip_y, int32_t mode_center,
                                      float focal, float* rays_o, float* rays_d, float* viewdirs, void* stream) {
     REQ(H > 0 && W > 0 && K_dev && c2w_dev && rays_o && rays_d && viewdirs);
-    // -1./(W/(2.*focal)) as the reference evaluates it: Python double arithmetic, cast to fp32 by the tensor multiply
-    const float c_w = (float)(-1.0 / ((double)W / (2.0 * (double)focal)));
-    const float c_h = (float)(-1.0 / ((double)H / (2.0 * (double)focal)));
+    const float c_w = k4s_ndc_scale(W, focal), c_h = k4s_ndc_scale(H, focal);
     hipLaunchKernelGGL(k_rays_of_view, dim3(k4_blocks((int64_t)H * W)), dim3(K4_THREADS), 0, ST, H, W, K_dev, c2w_dev, ndc, inverse_y,
                        flip_x, flip_y, mode_center ? 0.5f : 0.f, c_w, c_h, rays_o, rays_d, viewdirs);
     return k4_check_launch();

@@ -634,6 +634,39 @@ class DirectVoxGO(torch.nn.Module, _VoxGOCommon):
         return count
 
     @torch.no_grad()
+    def k4_voxel_count_views(self, rays_o_tr, rays_d_tr, imsz, near, far, stepsize, downrate=1, irregular_shape=False):
+        """``voxel_count_views`` on a fused ray walk: per view one launch that adds every sample's trilinear weights to a fixed-point image
+        (k4_count_views_walk: the staged samples and weights bit for bit, zero padding included, no sample list in memory) and one that counts
+        the voxels past 1 and clears the image (k4_count_views_finalise).  Integer sums: the count does not depend on the order of the rays and
+        repeats bit for bit.  Rays may be CPU tensors: a view crosses to the device once.  ``far`` is ignored, as upstream."""
+        n_samples = int(np.linalg.norm(np.array(self.world_size.cpu()) + 1) / stepsize) + 1
+        count = torch.zeros_like(self.density.get_dense_grid())
+        dev = count.device
+        if dev.type != 'cuda':
+            raise N.K4Error('k4_voxel_count_views: the model must be on the GPU (no CPU path exists for this op)')
+        step = float(stepsize * self.voxel_size)                       # the fp32 scalar product the staged expression forms first
+        acc = torch.zeros(list(count.shape[2:]), dtype=torch.int64, device=dev)
+
+        def on_device(piece):
+            if not irregular_shape:
+                piece = piece[::downrate, ::downrate].flatten(0, -2)   # the reference's literal slice (lib/dvgo.py:249)
+            return piece.to(dev).float().contiguous()
+        for rays_o, rays_d in zip(rays_o_tr.split(imsz), rays_d_tr.split(imsz)):
+            render_utils_cuda.count_views_walk(on_device(rays_o), on_device(rays_d), self.xyz_min, self.xyz_max, near, step, n_samples, acc)
+            render_utils_cuda.count_views_finalise(acc, count)
+        return count
+
+    @torch.no_grad()
+    def k4_maskout_near_cam_vox(self, cam_o, near_clip):
+        """``maskout_near_cam_vox`` in one launch (k4_near_cam_mask): a thread per grid node loops over the cameras, no [X, Y, Z, n_cam, 3] table."""
+        if not hasattr(self.density, 'grid'):
+            raise NotImplementedError(f'maskout_near_cam_vox writes density.grid: not available for a {type(self.density).__name__} density (as upstream)')
+        g = self.density.grid
+        axes = grid.grid_axes(self.xyz_min, self.xyz_max, self.world_size.tolist())
+        render_utils_cuda.near_cam_mask(axes, cam_o.to(g.device).float().contiguous(), near_clip, g.data)
+        torch.autograd.graph.increment_version(g)
+
+    @torch.no_grad()
     def hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         '''Which rays meet an occupied cell of the mask cache (lib/dvgo.py:281-293)?  Rays of any leading shape -> bool of that shape.'''
         shape = rays_o.shape[:-1]

@@ -867,9 +867,13 @@ def occupancy_from_alpha(alpha, thres):
 
 def grid_nodes(xyz_min, xyz_max, shape):
     """World positions of the nodes of an [X,Y,Z] grid spanning the bbox (the meshgrid of linspaces of lib/dmpigo.py:199-203)."""
+    return torch.stack(torch.meshgrid(*grid_axes(xyz_min, xyz_max, shape), indexing='ij'), -1)
+
+
+def grid_axes(xyz_min, xyz_max, shape):
+    """The three 1-D node coordinate axes ``grid_nodes`` is the meshgrid of."""
     dev = xyz_min.device
-    axes = [torch.linspace(float(xyz_min[i]), float(xyz_max[i]), int(shape[i]), device=dev) for i in range(3)]
-    return torch.stack(torch.meshgrid(*axes, indexing='ij'), -1)
+    return [torch.linspace(float(xyz_min[i]), float(xyz_max[i]), int(shape[i]), device=dev) for i in range(3)]
 
 
 class MaskGrid(nn.Module):

@@ -129,6 +129,62 @@ def patch_hit_counts(hit, bs):
     return counts
 
 
+# ---- scene preparation (csrc/k4_prep.hip): not among the reference's 13 either -----------------------------------------------------------------
+def count_views_walk(rays_o, rays_d, xyz_min, xyz_max, near, step, n_samples, acc):
+    """One view of ``voxel_count_views``: the trilinear weights of every sample of rays [n, 3] added to acc [X, Y, Z] (int64 storage of the unsigned
+    32.32 fixed-point sums), no sample list in memory (k4_count_views_walk)."""
+    X, Y, Z = (int(v) for v in acc.shape)
+    if acc.dtype != torch.int64:
+        raise N.K4Error(f'count_views_walk: int64 accumulator expected, got {acc.dtype}')
+    N.check(N.lib().k4_count_views_walk(N.f32(rays_o), N.f32(rays_d), rays_o.shape[0], N.f32(xyz_min), N.f32(xyz_max), X, Y, Z, _f(near), _f(step),
+                                        int(n_samples), N.ptr(acc), N.stream()), 'count_views_walk')
+
+
+def count_views_finalise(acc, count):
+    """count += (acc > 1.0); acc = 0 (k4_count_views_finalise).  count: fp32 with acc's number of elements."""
+    if acc.dtype != torch.int64 or count.numel() != acc.numel():
+        raise N.K4Error('count_views_finalise: an int64 accumulator and a count of the same size expected')
+    N.check(N.lib().k4_count_views_finalise(N.ptr(acc), N.f32(count), acc.numel(), N.stream()), 'count_views_finalise')
+
+
+def near_cam_mask(axes, cam_o, near_clip, density):
+    """density [.., X, Y, Z] (in place) = -100 at the nodes (axes[0][i], axes[1][j], axes[2][k]) within near_clip of a camera centre (k4_near_cam_mask)."""
+    X, Y, Z = (int(a.shape[0]) for a in axes)
+    if density.numel() != X * Y * Z:
+        raise N.K4Error('near_cam_mask: the density grid does not have the axes\' shape')
+    N.check(N.lib().k4_near_cam_mask(N.f32(axes[0]), N.f32(axes[1]), N.f32(axes[2]), X, Y, Z, N.f32(cam_o), cam_o.shape[0], _f(near_clip),
+                                     N.f32(density), N.stream()), 'near_cam_mask')
+
+
+def _order_key(x):
+    """fp32 <-> int32 with the same order (its own inverse; k4p_key of csrc/k4_prep.hip)."""
+    k = x.view(torch.int32)
+    return k ^ ((k >> 31) & 0x7fffffff)
+
+
+def frustum_bounds(hw, Ks, c2ws, ndc_scale, max_pixels, ndc, inverse_y, flip_x, flip_y, use_viewdirs, ts):
+    """Per view min / max of the points o + dir * t, t in ts (one or two values), over the rays of get_rays_of_a_view: hw int32 [n, 2], Ks [n, 3, 3],
+    c2ws [n, 3, 4], ndc_scale [n, 2] on the device -> fp32 [n, 6] = min xyz, max xyz (k4_frustum_bounds)."""
+    n = int(hw.shape[0])
+    if hw.dtype != torch.int32 or tuple(Ks.shape) != (n, 3, 3) or tuple(c2ws.shape) != (n, 3, 4) or tuple(ndc_scale.shape) != (n, 2):
+        raise N.K4Error('frustum_bounds: hw int32 [n, 2], Ks [n, 3, 3], c2ws [n, 3, 4], ndc_scale [n, 2] expected')
+    inf = torch.full([n, 3], float('inf'), dtype=torch.float32, device=hw.device)
+    keys = _order_key(torch.cat([inf, -inf], 1).contiguous()).contiguous()
+    N.check(N.lib().k4_frustum_bounds(N.ptr(hw), N.f32(Ks), N.f32(c2ws), N.f32(ndc_scale), n, int(max_pixels), int(bool(ndc)), int(bool(inverse_y)),
+                                      int(bool(flip_x)), int(bool(flip_y)), int(bool(use_viewdirs)), len(ts), _f(ts[0]), _f(ts[-1]),
+                                      N.ptr(keys), N.stream()), 'frustum_bounds')
+    return _order_key(keys).view(torch.float32)
+
+
+def coarse_geo_bounds(density, act_shift, interval, thres):
+    """density [X, Y, Z] -> int32 [6] on the device: min / max node index per axis where raw2alpha(density + act_shift, interval) > thres;
+    {INT32_MAX x 3, -1 x 3} when no node passes (k4_coarse_geo_bounds)."""
+    X, Y, Z = (int(v) for v in density.shape)
+    out = torch.tensor([2 ** 31 - 1] * 3 + [-1] * 3, dtype=torch.int32).to(density.device)
+    N.check(N.lib().k4_coarse_geo_bounds(N.f32(density), X, Y, Z, _f(act_shift), _f(interval), _f(thres), N.ptr(out), N.stream()), 'coarse_geo_bounds')
+    return out
+
+
 def _raw2alpha(density, shift, interval, ipp):
     exp_d = torch.empty_like(density)
     alpha = torch.empty_like(density)

@@ -1065,6 +1065,37 @@ typedef struct k4_vq_desc {
 } k4_vq_desc;
 int k4_march_vq_fwd(const k4_vq_desc* desc, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scene preparation (csrc/k4_prep.hip): what run_sr.py computes once before the first iteration.  Added under ABI 24 without a bump, as the
+ * scatter-image entry points were: they break no caller, and the loader refuses a library that lacks any of them.
+ * ------------------------------------------------------------------------------------------- */
+/* DirectVoxGO.voxel_count_views (lib/dvgo.py:235-268), one view: the walk adds the trilinear weights of every sample of rays [n_rays][3] -- sample i of
+ * a ray at t_min + (step * i) / |d|, i < n_samples, t_min = the box entry clamped to [near, 1e9], every operation rounded as the tensor expression
+ * rounds it, zero padding included (a sample outside the box feeds those of its corners that are grid nodes) -- to acc [X][Y][Z], 64-bit unsigned
+ * 32.32 fixed point, with integer atomics: no sample list reaches memory, the sums do not depend on the order of the rays.  acc must be all zero before
+ * a view's first walk; it cannot wrap for any n_rays (csrc/k4_prep.hip states why).  step = stepsize * voxel_size as an fp32 product; xyz_min / xyz_max:
+ * DEVICE pointers.  The finalise pass is sampler-independent: count[i] += (acc[i] > 1.0), acc[i] = 0. */
+int k4_count_views_walk(const float* rays_o, const float* rays_d, int64_t n_rays, const float* xyz_min, const float* xyz_max,
+                        int32_t X, int32_t Y, int32_t Z, float near, float step, int32_t n_samples, uint64_t* acc, void* stream);
+int k4_count_views_finalise(uint64_t* acc, float* count, int64_t n_voxels, void* stream);
+/* DirectVoxGO.maskout_near_cam_vox (lib/dvgo.py:186-198): density [X][Y][Z] = -100 at the nodes (axis_x[i], axis_y[j], axis_z[k]) whose distance
+ * sqrt((dx*dx + dy*dy) + dz*dz) to the nearest of cam_o [n_cam][3] is <= near_clip.  One launch, nothing but the density is written. */
+int k4_near_cam_mask(const float* axis_x, const float* axis_y, const float* axis_z, int32_t X, int32_t Y, int32_t Z, const float* cam_o,
+                     int32_t n_cam, float near_clip, float* density, void* stream);
+/* compute_bbox_by_cam_frustrm (run_sr.py:222-268) over all views in one launch.  Per view v: hw [v][2] = (H, W), Ks [v][9], c2ws [v][12] (rows of 4),
+ * ndc_scale [v][2] = -1/(W/(2 focal)), -1/(H/(2 focal)) as fp32 (used when ndc), all on the DEVICE; max_pixels = max H * W.  Per pixel the ray of
+ * k4_get_rays_of_a_view (pixel centres) and the points o + dir * t0 (and o + dir * t1 when n_t == 2), dir = viewdirs when use_viewdirs, else rays_d.
+ * keys [v][6]: min x, y, z / max x, y, z per view as order-preserving integers (k ^ ((k >> 31) & 0x7fffffff) of the fp32 bits, its own inverse); the
+ * caller fills them with the keys of +inf / -inf and takes the final min / max over the views. */
+int k4_frustum_bounds(const int32_t* hw, const float* Ks, const float* c2ws, const float* ndc_scale, int32_t n_views, int64_t max_pixels,
+                      int32_t ndc, int32_t inverse_y, int32_t flip_x, int32_t flip_y, int32_t use_viewdirs, int32_t n_t, float t0, float t1,
+                      int32_t* keys, void* stream);
+/* compute_bbox_by_coarse_geo (run_sr.py:271-291): out6 = min x, y, z / max x, y, z of the node indices of density [X][Y][Z] with
+ * raw2alpha(density + act_shift, interval) > thres, exact (integer atomics).  The caller fills out6 with {INT32_MAX x 3, -1 x 3}: no node passes
+ * when it comes back unchanged. */
+int k4_coarse_geo_bounds(const float* density, int32_t X, int32_t Y, int32_t Z, float act_shift, float interval, float thres, int32_t* out6,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
