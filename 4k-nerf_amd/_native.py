@@ -66,6 +66,18 @@ class VqDesc(C.Structure):             # k4_vq_desc (ABI 22)
                 ('rgb', C.c_void_p), ('depth', C.c_void_p), ('alphainv_last', C.c_void_p)]
 
 
+class DirectTrainDesc(C.Structure):    # k4_direct_train_desc (added under ABI 24)
+    _fields_ = [('rays_o', C.c_void_p), ('rays_d', C.c_void_p), ('target', C.c_void_p), ('n_rays', C.c_int64),
+                ('density', C.c_void_p), ('k0', C.c_void_p), ('density_ch', C.c_int32), ('k0_ch', C.c_int32), ('k0_layout', C.c_int32), ('dims', C.c_int32 * 3),
+                ('xyz_min', C.c_void_p), ('xyz_max', C.c_void_p),
+                ('mask', C.c_void_p), ('mask_dims', C.c_int32 * 3), ('xyz2ijk_scale', C.c_void_p), ('xyz2ijk_shift', C.c_void_p),
+                ('near', C.c_float), ('stepdist', C.c_float), ('max_steps', C.c_int32), ('act_shift', C.c_float), ('interval', C.c_float),
+                ('fast_color_thres', C.c_float), ('bg', C.c_float),
+                ('weight_main', C.c_float), ('weight_entropy_last', C.c_float), ('weight_rgbper', C.c_float),
+                ('rgb_marched', C.c_void_p), ('alphainv_last', C.c_void_p), ('n_shaded', C.c_void_p), ('end_step', C.c_void_p), ('partials', C.c_void_p),
+                ('ckpt', C.c_void_p), ('chunk_mask', C.c_void_p)]
+
+
 class MlpDesc(C.Structure):
     _fields_ = [('packed', C.c_void_p), ('dim0', C.c_int32), ('width', C.c_int32), ('n_hidden', C.c_int32),
                 ('viewbase_pe', C.c_int32), ('spatial_pe', C.c_int32), ('k0_skip', C.c_int32), ('arith', C.c_int32)]
@@ -316,6 +328,9 @@ _EXTRA_SIGS = {
     'k4_near_cam_mask': ([_P, _P, _P, _I32, _I32, _I32, _P, _I32, _F, _P, _P], C.c_int),
     'k4_frustum_bounds': ([_P, _P, _P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P], C.c_int),
     'k4_coarse_geo_bounds': ([_P, _I32, _I32, _I32, _F, _F, _F, _P, _P], C.c_int),
+    'k4_direct_train_chunks': ([_I32], C.c_int32),
+    'k4_direct_train_fwd': ([C.POINTER(DirectTrainDesc), _P, _P, _P], C.c_int),
+    'k4_direct_train_bwd': ([C.POINTER(DirectTrainDesc), _P, _P, _P, _P], C.c_int),
     'k4_frame_metrics': ([_P, _I64, _I64, _I32, _P, _I64, _I64, _I32, _I32, _I32, C.POINTER(C.c_double), _I32, C.c_double, C.c_double, _P, _P, _P, _P], C.c_int),
 }
 

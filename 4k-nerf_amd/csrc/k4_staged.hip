@@ -20,26 +20,8 @@ __device__ __forceinline__ void k4s_ndc_point(const float* __restrict__ o, const
     p[1] = fmaf(d[ray * 3 + 1], dist, o[ray * 3 + 1]);
     p[2] = fmaf(d[ray * 3 + 2], dist, o[ray * 3 + 2]);
 }
-__device__ __forceinline__ bool k4s_outbbox(const float (&p)[3], const float* __restrict__ mn, const float* __restrict__ mx) {
-    return (mn[0] > p[0]) | (mn[1] > p[1]) | (mn[2] > p[2]) | (mx[0] < p[0]) | (mx[1] < p[1]) | (mx[2] < p[2]);
-}
-__device__ __forceinline__ uint8_t k4s_maskcache(const uint8_t* __restrict__ world, float x, float y, float z, const float* __restrict__ sc,
-                                                 const float* __restrict__ sh, int si, int sj, int sk) {
-    const int a = k4_round_half_away(fmaf(x, sc[0], sh[0]));
-    const int b = k4_round_half_away(fmaf(y, sc[1], sh[1]));
-    const int c = k4_round_half_away(fmaf(z, sc[2], sh[2]));
-    uint8_t v = 0;
-    if ((unsigned)a < (unsigned)si && (unsigned)b < (unsigned)sj && (unsigned)c < (unsigned)sk)
-        v = world[((size_t)a * sj + b) * sk + c] != 0;
-    return v;
-}
-// (k4s_grid_corners, k4s_raw2alpha and k4s_ray_of_pixel: k4_staged_ops.h, shared with k4_prep.hip)
-__device__ __forceinline__ float k4s_grid_blend(const float* __restrict__ g, const size_t (&idx)[8], const float (&w)[8]) {
-    float v = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) v += g[idx[c]] * w[c];
-    return v;
-}
+// (k4s_outbbox, k4s_maskcache, k4s_grid_blend, k4s_grid_corners, k4s_raw2alpha and k4s_ray_of_pixel: k4_staged_ops.h, shared with k4_prep.hip and
+//  k4_direct_train.hip)
 
 // ---------------------------------------------------------------- sample_ndc_pts_on_rays (.cu:245-270)
 __global__ void k_sample_ndc(const float* __restrict__ o, const float* __restrict__ d,
@@ -56,23 +38,7 @@ __global__ void k_sample_ndc(const float* __restrict__ o, const float* __restric
 }
 
 // ---------------------------------------------------------------- ray-AABB helpers (.cu:12-79)
-__device__ __forceinline__ void aabb_t(const float* o, const float* d, const float* mn, const float* mx,
-                                        float near, float far, int64_t r, float& t_min, float& t_max) {
-    const float vx = d[r * 3 + 0] == 0.f ? 1e-6f : d[r * 3 + 0];
-    const float vy = d[r * 3 + 1] == 0.f ? 1e-6f : d[r * 3 + 1];
-    const float vz = d[r * 3 + 2] == 0.f ? 1e-6f : d[r * 3 + 2];
-    const float ax = (mx[0] - o[r * 3 + 0]) / vx, ay = (mx[1] - o[r * 3 + 1]) / vy, az = (mx[2] - o[r * 3 + 2]) / vz;
-    const float bx = (mn[0] - o[r * 3 + 0]) / vx, by = (mn[1] - o[r * 3 + 1]) / vy, bz = (mn[2] - o[r * 3 + 2]) / vz;
-    t_min = fmaxf(fminf(fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz)), far), near);
-    t_max = fmaxf(fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)), far), near);
-}
-__device__ __forceinline__ float ray_norm(const float* d, int64_t r) {
-    return sqrtf(fmaf(d[r * 3 + 2], d[r * 3 + 2], fmaf(d[r * 3 + 1], d[r * 3 + 1], d[r * 3 + 0] * d[r * 3 + 0])));
-}
-__device__ __forceinline__ int64_t n_steps_of(float t_min, float t_max, float rnorm, float stepdist) {
-    return (int64_t)fmaxf(ceilf((t_max - t_min) * rnorm / stepdist), 1.f);      // at least 1 point (.cu:53)
-}
-
+// (aabb_t, ray_norm, n_steps_of: k4_staged_ops.h)
 __global__ void k_t_minmax(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ mn,
                            const float* __restrict__ mx, float near, float far, int64_t n,
                            float* __restrict__ tmin, float* __restrict__ tmax) {
@@ -230,7 +196,7 @@ __global__ void k_raw2alpha_bwd(const float* __restrict__ ex, const float* __res
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float iv = ipp ? ipp[i] : interval;
-    g[i] = fminf(ex[i], 1e10f) * powf(1.f + ex[i], -iv - 1.f) * iv * gb[i];
+    g[i] = K4S_RAW2ALPHA_BWD(ex[i], iv, gb[i]);
 }
 
 // ---------------------------------------------------------------- alpha2weight (.cu:577-651)

@@ -1,6 +1,6 @@
 // Per-sample / per-pixel arithmetic of the staged kernels (k4_staged.hip) that other translation units must repeat BIT FOR BIT: the trilinear
 // corner set of the grid lookup, the density activation and the ray of a pixel.  One expression tree each, inlined wherever it is used
-// (k4_staged.hip, k4_prep.hip): a decision taken on these values in one file is the decision the staged op sequence takes.
+// (k4_staged.hip, k4_prep.hip, k4_direct_train.hip): a decision taken on these values in one file is the decision the staged op sequence takes.
 #pragma once
 #include "k4_common.h"
 
@@ -28,6 +28,47 @@ __device__ __forceinline__ void k4s_grid_corners(float x, float y, float z, cons
 __device__ __forceinline__ void k4s_raw2alpha(float den, float shift, float iv, float& e, float& al) {
     e = expf(den + shift);
     al = (iv == 1.f) ? 1.f - 1.f / (1.f + e) : 1.f - powf(1.f + e, -iv);
+}
+// its backward (.cu:507-530): d alpha / d density times the incoming gradient, from the saved e = exp(density + shift).  A macro, so that
+// k_raw2alpha_bwd (k4_staged.hip) keeps the expression it always had, token for token, and with it its code object.
+#define K4S_RAW2ALPHA_BWD(e, iv, g) (fminf((e), 1e10f) * powf(1.f + (e), -(iv) - 1.f) * (iv) * (g))
+
+// the out-of-box test, the mask cache and the blend of a lookup (moved here verbatim from k4_staged.hip)
+__device__ __forceinline__ bool k4s_outbbox(const float (&p)[3], const float* __restrict__ mn, const float* __restrict__ mx) {
+    return (mn[0] > p[0]) | (mn[1] > p[1]) | (mn[2] > p[2]) | (mx[0] < p[0]) | (mx[1] < p[1]) | (mx[2] < p[2]);
+}
+__device__ __forceinline__ uint8_t k4s_maskcache(const uint8_t* __restrict__ world, float x, float y, float z, const float* __restrict__ sc,
+                                                 const float* __restrict__ sh, int si, int sj, int sk) {
+    const int a = k4_round_half_away(fmaf(x, sc[0], sh[0]));
+    const int b = k4_round_half_away(fmaf(y, sc[1], sh[1]));
+    const int c = k4_round_half_away(fmaf(z, sc[2], sh[2]));
+    uint8_t v = 0;
+    if ((unsigned)a < (unsigned)si && (unsigned)b < (unsigned)sj && (unsigned)c < (unsigned)sk)
+        v = world[((size_t)a * sj + b) * sk + c] != 0;
+    return v;
+}
+__device__ __forceinline__ float k4s_grid_blend(const float* __restrict__ g, const size_t (&idx)[8], const float (&w)[8]) {
+    float v = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v += g[idx[c]] * w[c];
+    return v;
+}
+// ray-AABB helpers (.cu:12-79; moved here verbatim from k4_staged.hip)
+__device__ __forceinline__ void aabb_t(const float* o, const float* d, const float* mn, const float* mx,
+                                        float near, float far, int64_t r, float& t_min, float& t_max) {
+    const float vx = d[r * 3 + 0] == 0.f ? 1e-6f : d[r * 3 + 0];
+    const float vy = d[r * 3 + 1] == 0.f ? 1e-6f : d[r * 3 + 1];
+    const float vz = d[r * 3 + 2] == 0.f ? 1e-6f : d[r * 3 + 2];
+    const float ax = (mx[0] - o[r * 3 + 0]) / vx, ay = (mx[1] - o[r * 3 + 1]) / vy, az = (mx[2] - o[r * 3 + 2]) / vz;
+    const float bx = (mn[0] - o[r * 3 + 0]) / vx, by = (mn[1] - o[r * 3 + 1]) / vy, bz = (mn[2] - o[r * 3 + 2]) / vz;
+    t_min = fmaxf(fminf(fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz)), far), near);
+    t_max = fmaxf(fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)), far), near);
+}
+__device__ __forceinline__ float ray_norm(const float* d, int64_t r) {
+    return sqrtf(fmaf(d[r * 3 + 2], d[r * 3 + 2], fmaf(d[r * 3 + 1], d[r * 3 + 1], d[r * 3 + 0] * d[r * 3 + 0])));
+}
+__device__ __forceinline__ int64_t n_steps_of(float t_min, float t_max, float rnorm, float stepdist) {
+    return (int64_t)fmaxf(ceilf((t_max - t_min) * rnorm / stepdist), 1.f);      // at least 1 point (.cu:53)
 }
 
 // get_rays_of_a_view (lib/dvgo.py:516-582) for ONE pixel: pixel -> camera direction -> world ray -> unit view direction (BEFORE the NDC

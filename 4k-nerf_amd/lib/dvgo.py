@@ -752,6 +752,45 @@ class DirectVoxGO(torch.nn.Module, _VoxGOCommon):
             None if k4_counters is None else N.ptr(k4_counters), N.stream()), 'k4_march_dvgo_fwd')
         return ret
 
+    def k4_direct_train_supported(self, **render_kwargs):
+        """Can ``train_ops.dvgo_direct_render_loss`` run this model's training step (k4_direct_train_fwd / _bwd)?  -> (bool, reason).
+        The class: direct colour (no rgbnet, three k0 channels), DenseGrid density and k0 of one shape, a mask cache, a fixed background,
+        CUDA fp32 parameters."""
+        if self.rgbnet is not None:
+            return False, 'the model has an rgbnet: only direct colour, rgb = sigmoid(k0), is covered'
+        for name, g in (('density', self.density), ('k0', self.k0)):
+            if not isinstance(g, grid.DenseGrid):
+                return False, f'{name} is a {type(g).__name__}: only DenseGrid is covered'
+        if self.k0_dim != 3 or self.k0.grid.shape[1] != 3 or self.density.grid.shape[1] != 1:
+            return False, f'k0 has {self.k0.grid.shape[1]} channels and density {self.density.grid.shape[1]}: 3 and 1 are covered'
+        if self.k0.grid.shape[2:] != self.density.grid.shape[2:]:
+            return False, 'density and k0 differ in shape'
+        if getattr(self, 'mask_cache', None) is None:
+            return False, 'the model has no mask cache'
+        if render_kwargs.get('rand_bkgd', False):
+            return False, 'rand_bkgd: a random background per ray is not covered'
+        for name, t in (('density.grid', self.density.grid), ('k0.grid', self.k0.grid)):
+            if not t.is_cuda:
+                return False, f'{name} is not on the GPU (no CPU path exists for this op)'
+            if t.dtype != torch.float32:
+                return False, f'{name} is {t.dtype}: fp32 parameters are covered'
+        return True, ''
+
+    def _k4_direct_train_steps(self, stepsize):
+        """(stepdist, interval, act_shift, an upper bound of any ray's steps) of the fused training step, per (stepsize, resolution, box); one
+        read-back of the box diagonal per key, none per call."""
+        c = self._k4_cache()
+        key = (float(stepsize), float(self.voxel_size), float(self.voxel_size_ratio), self.xyz_min.data_ptr(), self.xyz_min._version,
+               self.xyz_max.data_ptr(), self.xyz_max._version)
+        hit = c.get('direct_train_steps')
+        if hit is None or hit[0] != key:
+            sd = float(stepsize * self.voxel_size)                         # lib/dvgo.py:310
+            itv = float(stepsize * self.voxel_size_ratio)                  # lib/dvgo.py:341
+            diag = float((self.xyz_max - self.xyz_min).norm())
+            hit = c['direct_train_steps'] = (key, (sd, itv, int(np.ceil(diag / sd)) + 2))
+        sd, itv, max_steps = hit[1]
+        return sd, itv, self._k4_host_scalar('act_shift', self.act_shift), max_steps
+
     def _forward_staged(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, **_ignored):
         """The reference's op sequence (lib/dvgo.py:338-446) on the staged gfx950 kernels."""
         ret_dict = {}

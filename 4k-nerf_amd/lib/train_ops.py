@@ -11,6 +11,9 @@
                         hidden->hidden layer, dim0 > 64; ``rgbnet_supported`` tells which): layer by layer on the exact-fp32 1x1 MFMA
                         convolution, INFERENCE ONLY -- the models route such shapes here (lib/dvgo.py::_k4_rgbnet_sigmoid).
 
+``dvgo_direct_render_loss`` one training step of the direct-colour ``DirectVoxGO`` (``rgbnet_dim=0``; run_sr.py:516-547): render, loss terms and the
+                        gradients of ``density.grid`` / ``k0.grid`` on a fused forward / backward walk (csrc/k4_direct_train.hip), opt-in.
+
 There is no CPU path and no PyTorch path: CPU tensors raise ``K4Error``; so do these out-of-shape stacks under autograd, and anything that is
 not a biased Linear-ReLU stack ending in 3 outputs (another activation, a bias-free Linear, a layer wider than 128 / more than 192 inputs).
 """
@@ -309,3 +312,105 @@ def flatten_eff_distloss(w, s, interval, ray_id, n_rays=None):
     package's signature): the number of rays of the batch -- any integer > max(ray_id) -- saves the host synchronisation that reading
     ``ray_id.max()`` back costs."""
     return FlattenEffDistLoss.apply(w, s, interval, ray_id, n_rays)
+
+
+def direct_train_table(n_rays, max_steps):
+    """(chunks per ray, floats of the transmittance checkpoint table) of the fused direct-colour training step: a ray is walked 64 steps at a
+    time and the transmittance at the start of every chunk is kept for the backward's replay (k4_direct_train_chunks).  Raises outside the
+    covered range (1..4096 steps)."""
+    chunks = int(N.lib().k4_direct_train_chunks(int(max_steps)))
+    if chunks < 0:
+        raise N.K4Error(f'dvgo_direct_render_loss: {max_steps} steps per ray are outside the checkpoint table (1..4096)')
+    return chunks, int(n_rays) * chunks
+
+
+class DvgoDirectRenderLoss(torch.autograd.Function):
+    """Render + loss of the direct-colour DirectVoxGO as ONE node over (density.grid, k0.grid): k4_direct_train_fwd (the walk and the ordered
+    reduction of the loss terms), k4_direct_train_bwd (one launch on the device scalar grad_total) into dense gradients in the parameters' layout."""
+
+    @staticmethod
+    def forward(ctx, density, k0, desc, keep):
+        dev = density.device
+        terms = torch.empty([4], dtype=torch.float32, device=dev)
+        total = torch.empty([], dtype=torch.float32, device=dev)
+        N.check(N.lib().k4_direct_train_fwd(N.C.byref(desc), N.f32(terms), N.f32(total), N.stream()), 'k4_direct_train_fwd')
+        # the backward launch re-reads the grids and the forward's per-ray outputs through the descriptor's raw pointers: the grids are saved (autograd
+        # raises if one is written in place before backward), the outputs' versions are noted (two of them are handed to the caller)
+        ctx.save_for_backward(density, k0)
+        ctx.desc, ctx.keep = desc, keep
+        ctx.versions = [(t, t._version) for t in keep if torch.is_tensor(t)]
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, _g_terms):
+        density, k0 = ctx.saved_tensors                     # (the version check of the parameters)
+        if density.data_ptr() != ctx.desc.density or k0.data_ptr() != ctx.desc.k0:
+            raise N.K4Error('dvgo_direct_render_loss: a grid was moved between forward and backward')
+        for t, v in ctx.versions:
+            if t._version != v:
+                raise N.K4Error('dvgo_direct_render_loss: a tensor the backward re-reads (rays, target, rgb_marched, alphainv_last or another output of '
+                                'the forward) was modified in place between forward and backward')
+        dev = g_total.device
+        g = g_total.detach().to(torch.float32).contiguous()
+        g_density = torch.zeros(density.shape, dtype=torch.float32, device=dev)
+        g_k0 = torch.zeros(k0.shape, dtype=torch.float32, device=dev)
+        N.check(N.lib().k4_direct_train_bwd(N.C.byref(ctx.desc), N.f32(g), N.f32(g_density), N.f32(g_k0), N.stream()), 'k4_direct_train_bwd')
+        return g_density, g_k0, None, None
+
+
+def dvgo_direct_render_loss(model, rays_o, rays_d, target, *, near, stepsize, bg, weight_main, weight_entropy_last=0.0, weight_rgbper=0.0,
+                            weight_nearclip=0.0, weight_distortion=0.0, **ignored):
+    """One training step's render and loss of a direct-colour ``DirectVoxGO`` (``rgbnet_dim=0``) on a fused forward / backward walk: what
+    ``model(rays_o, rays_d, viewdirs, **render_kwargs)`` under autograd plus the loss lines of run_sr.py:523-546 compute, in two launches
+    (k4_direct_train_fwd), with one more for ``total.backward()`` (k4_direct_train_bwd) -- no sample list in memory, no host synchronisation.
+
+    -> dict: ``total`` (0-dim, with a grad_fn over ``density.grid`` and ``k0.grid``), ``terms`` {'photo', 'entropy', 'rgbper'} (detached device
+    scalars; a weight of 0 switches its term off), ``psnr`` (-10 log10(photo)), ``rgb_marched`` [N, 3], ``alphainv_last`` [N].
+    ``total.backward()`` leaves ordinary dense ``.grad`` tensors; it re-reads the grids, the rays, the target and the returned tensors, so writing any
+    of them in place before ``backward()`` raises.  Opt-in: ``DirectVoxGO.forward`` is untouched.  A model outside the covered
+    class (``model.k4_direct_train_supported``) raises ``K4Error`` with the reason; so do the nearclip and distortion terms."""
+    ok, why = model.k4_direct_train_supported(**ignored)
+    if not ok:
+        raise N.K4Error(f'dvgo_direct_render_loss: {why}')
+    if weight_nearclip or weight_distortion:
+        raise N.K4Error('dvgo_direct_render_loss: the nearclip and distortion terms are not covered (their weights are 0 in the coarse stage)')
+    for gr in (model.density, model.k0):
+        if not gr.grad_route.idle:
+            raise N.K4Error('dvgo_direct_render_loss: a grid is armed for a sparse / split gradient route or holds a seed; this step returns dense gradients')
+    ro, rd, tgt = (t.detach().float().contiguous() for t in (rays_o, rays_d, target))
+    if not (ro.is_cuda and rd.is_cuda and tgt.is_cuda):
+        raise N.K4Error('dvgo_direct_render_loss: rays and target must be on the GPU (no CPU path exists for this op)')
+    n = int(ro.shape[0])
+    if ro.shape != (n, 3) or rd.shape != (n, 3) or tgt.shape != (n, 3):
+        raise ValueError('dvgo_direct_render_loss: rays_o, rays_d and target are [N, 3]')
+    stepdist, interval, act_shift, max_steps = model._k4_direct_train_steps(stepsize)
+    chunks, table = direct_train_table(n, max_steps)
+    model._k4_params_ready()
+    dens, k0, mc, dev = model.density.grid, model.k0.grid, model.mask_cache, ro.device
+    rgb = torch.empty([n, 3], dtype=torch.float32, device=dev)
+    ainv = torch.empty([n], dtype=torch.float32, device=dev)
+    ints = torch.empty([2, n], dtype=torch.int32, device=dev)
+    partials = torch.empty([n, 3], dtype=torch.float32, device=dev)
+    ckpt = torch.empty([table], dtype=torch.float32, device=dev)
+    cmask = torch.empty([n], dtype=torch.int64, device=dev)
+    mask = mc.mask if mc.mask.dtype == torch.uint8 else mc.mask.view(torch.uint8)
+    consts = [t.detach().float().contiguous() for t in (model.xyz_min, model.xyz_max, mc.xyz2ijk_scale, mc.xyz2ijk_shift)]
+    d = N.DirectTrainDesc()
+    d.rays_o, d.rays_d, d.target, d.n_rays = ro.data_ptr(), rd.data_ptr(), tgt.data_ptr(), n
+    d.density, d.k0, d.density_ch, d.k0_ch, d.k0_layout = dens.data_ptr(), k0.data_ptr(), int(dens.shape[1]), int(k0.shape[1]), N.K0_CHANNEL_MAJOR
+    d.dims = (N.C.c_int32 * 3)(*[int(v) for v in dens.shape[2:]])
+    d.xyz_min, d.xyz_max, d.xyz2ijk_scale, d.xyz2ijk_shift = (t.data_ptr() for t in consts)
+    d.mask, d.mask_dims = mask.data_ptr(), (N.C.c_int32 * 3)(*[int(v) for v in mask.shape])
+    d.near, d.stepdist, d.max_steps, d.act_shift, d.interval = float(near), stepdist, max_steps, act_shift, interval
+    d.fast_color_thres, d.bg = float(model.fast_color_thres), float(bg)
+    d.weight_main, d.weight_entropy_last, d.weight_rgbper = float(weight_main), float(weight_entropy_last), float(weight_rgbper)
+    d.rgb_marched, d.alphainv_last, d.n_shaded, d.end_step = rgb.data_ptr(), ainv.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr()
+    d.partials, d.ckpt, d.chunk_mask = partials.data_ptr(), ckpt.data_ptr(), cmask.data_ptr()
+    if not (dens.is_contiguous() and k0.is_contiguous() and mask.is_contiguous()):
+        raise N.K4Error('dvgo_direct_render_loss: the grids and the mask must be contiguous')
+    keep = [ro, rd, tgt, rgb, ainv, ints, partials, ckpt, cmask, mask, *consts]
+    total, terms = DvgoDirectRenderLoss.apply(dens, k0, d, keep)
+    return {'total': total, 'terms': {'photo': terms[0], 'entropy': terms[2], 'rgbper': terms[3]}, 'psnr': terms[1],
+            'rgb_marched': rgb, 'alphainv_last': ainv, 'n_shaded': ints[0]}

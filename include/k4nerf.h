@@ -1096,6 +1096,45 @@ int k4_frustum_bounds(const int32_t* hw, const float* Ks, const float* c2ws, con
 int k4_coarse_geo_bounds(const float* density, int32_t X, int32_t Y, int32_t Z, float act_shift, float interval, float thres, int32_t* out6,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One training step of the direct-colour DirectVoxGO (csrc/k4_direct_train.hip), added under ABI 24 without a bump, as the scene-preparation entry points
+ * were (they break no caller, and the loader refuses a library that lacks any of them): rgbnet_dim = 0, rgb = sigmoid(k0), the loss lines of
+ * run_sr.py:523-546 (photo, its PSNR, last-transmittance entropy, per-sample colour) and the gradients of density.grid and k0.grid, in three launches
+ * with no per-sample value in memory and no host synchronisation.
+ *
+ * Covered: channel-major fp32 grids of one shape, density [1][X][Y][Z] and k0 [3][X][Y][Z] (k0_layout 0), max_steps <= 4096 (64 chunks of 64 steps:
+ * the checkpoint table and the per-ray chunk mask).  Anything else: K4_ERR_UNSUPPORTED.  xyz_min / xyz_max / xyz2ijk_* are DEVICE pointers to 3 floats;
+ * mask: uint8 [mask_dims]; far is 1e9, as upstream.  max_steps bounds the steps of any ray; a longer ray is cut there (nothing is written past a table) and
+ * reported: its rgb_marched, alphainv_last and partials are NaN, and so are the terms.
+ *
+ * k4_direct_train_chunks(max_steps) -> ceil(max_steps / 64), or -1 outside the covered range.
+ * k4_direct_train_fwd: per ray r (one wave, lanes = 64 consecutive steps in depth order; the staged op sequence's points, filters, transmittance product
+ *   and T < 1e-3 stop, bit for bit; fast_color_thres == 0 switches both `>` filters off) the caller-allocated outputs
+ *     rgb_marched [n][3] = sum w rgb + alphainv_last bg       alphainv_last [n]
+ *     n_shaded int32 [n]  the samples the staged list keeps     end_step int32 [n]  one past the last step that entered the product
+ *     partials [n][3]     sum_c (rgb_marched_c - target_c)^2,  p log p + (1 - p) log(1 - p) of p = clamp(alphainv_last, 1e-6, 1 - 1e-6),
+ *                         sum_m w_m |rgb_m - target|^2
+ *     ckpt [n][chunks]    the transmittance at the start of every chunk the walk entered      chunk_mask uint64 [n]  bit c: chunk c holds a sample of the product
+ *   then ONE workgroup sums the partials in fp64 in a fixed order: terms[4] = {photo = weight_main mean((rgb_marched - target)^2), psnr = -10 log10(photo),
+ *   entropy = -weight_entropy_last mean(.), rgbper = weight_rgbper sum(.) / n}, *total = photo + entropy + rgbper (device scalars; a weight of 0 switches
+ *   its term off).  The forward repeats bit for bit.
+ * k4_direct_train_bwd: with the SAME descriptor (inputs unchanged, outputs as the forward left them) and the device scalar *grad_total, adds the
+ *   gradients of `total` to grad_density [1][X][Y][Z] and grad_k0 [3][X][Y][Z] (the caller clears them) with float atomics: one launch, a ray's chunks
+ *   replayed from its far end.  Not bitwise reproducible from run to run, like the staged scatter.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct k4_direct_train_desc {
+    const float* rays_o; const float* rays_d; const float* target; int64_t n_rays;
+    const float* density; const float* k0; int32_t density_ch; int32_t k0_ch; int32_t k0_layout; int32_t dims[3];
+    const float* xyz_min; const float* xyz_max;
+    const uint8_t* mask; int32_t mask_dims[3]; const float* xyz2ijk_scale; const float* xyz2ijk_shift;
+    float near; float stepdist; int32_t max_steps; float act_shift; float interval; float fast_color_thres; float bg;
+    float weight_main; float weight_entropy_last; float weight_rgbper;
+    float* rgb_marched; float* alphainv_last; int32_t* n_shaded; int32_t* end_step; float* partials; float* ckpt; uint64_t* chunk_mask;
+} k4_direct_train_desc;
+int32_t k4_direct_train_chunks(int32_t max_steps);
+int k4_direct_train_fwd(const k4_direct_train_desc* desc, float* terms, float* total, void* stream);
+int k4_direct_train_bwd(const k4_direct_train_desc* desc, const float* grad_total, float* grad_density, float* grad_k0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
